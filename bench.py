@@ -14,8 +14,13 @@ operations run the production C++ code against a temp-dir cgroupfs/rootfs (the G
 unprivileged), and the probe kernels run on the real GPUs. By default (``--deploy processes``)
 the fake control plane, the worker and the master are separate processes started through the
 production entry points, as deployed; ``--deploy inprocess`` runs them on one event loop.
-After the timed loop the reference's call sequence is re-enacted in the same deployment shape
-(``reference_emulated_same_run``, gpumounter_amd/fakes/refproto.py).
+A plain run sets up, warms up, times ``--steps`` steps, writes the last step's outputs if
+``--dump-outputs`` is given, and prints the result line. Everything else the benchmark can measure
+or check runs only with ``--full``: the box calibration (``box``), the tenant-side view checks from
+fresh HIP and PyTorch processes, peer-to-peer bandwidth, the call accounting cycles, the idle/cold
+attach cycles, the final ledger audit and the daemons' counters, and the reference's call sequence
+re-enacted in the same deployment shape (``reference_emulated_same_run``,
+gpumounter_amd/fakes/refproto.py). Without ``--full`` their fields are null.
 
 Launch: ``python bench.py --gpus 1`` or, for N>1, under torch.distributed.run with one rank per GPU.
 Rank 0 hosts the control plane; all ranks take part in verification. Prints ONE JSON line on rank 0.
@@ -182,6 +187,18 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: box calibration, tenant-side view checks, "
+                         "peer-to-peer bandwidth, call accounting (--call-cycles), idle/cold "
+                         "attaches (--cold-steps), the final ledger audit and daemon counters, "
+                         "and the emulated reference (--ref-steps). A plain run does none of them")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its "
+                         "caller as DIR/<name>.npy (float64): attach_status (HTTP status of the "
+                         "attach and of the detach), attached_gpus (the attached GPUs as "
+                         "positions in the node's GPU list, ascending), audit_issues (ledger / "
+                         "cgroup / device-node disagreements found) and gpus_verified (1 per "
+                         "attached GPU whose liveness kernel ran)")
     ap.add_argument("--mode", choices=("entire", "single"), default="entire")
     ap.add_argument("--latency", choices=("zero", "realistic"), default="zero",
                     help="fake control-plane latency model (zero = controller overhead only)")
@@ -198,7 +215,7 @@ def main() -> int:
                     help="the worker serves amd.com/gpu itself; the fake kubelet's device manager "
                          "calls GetPreferredAllocation/Allocate on it at admission")
     ap.add_argument("--ref-steps", type=int, default=0,
-                    help="after the timed loop, re-run this many attach/detach cycles with the "
+                    help="--full: after the timed loop, this many attach/detach cycles with the "
                          "emulated reference protocol on the same cluster (only with --latency "
                          "zero and no warm pool). Off by default: it compares call sequences on "
                          "a zero-latency fake, not a published reference figure")
@@ -230,14 +247,14 @@ def main() -> int:
     ap.add_argument("--log-dir", default="",
                     help="--deploy processes: keep the daemons' logs in this directory")
     ap.add_argument("--cold-steps", type=int, default=10,
-                    help="after the timed loop (--deploy processes): restart the master with "
-                         "authz TTLs of --idle-s/2 and time this many attaches, each after "
+                    help="--full, after the timed loop (--deploy processes): restart the master "
+                         "with authz TTLs of --idle-s/2 and time this many attaches, each after "
                          "--idle-s of idleness, so each one finds its TokenReview and "
                          "SubjectAccessReview answers expired (cold_attach_p50_ms); 0 = skip")
     ap.add_argument("--idle-s", type=float, default=0.3,
                     help="idle time before each cold attach (see --cold-steps)")
     ap.add_argument("--no-calib", action="store_true",
-                    help="skip the box calibration (CPU loop, process pingpong, gRPC floor) "
+                    help="--full: no box calibration (CPU loop, process pingpong, gRPC floor) "
                          "recorded as \"box\" in the JSON")
     ap.add_argument("--pin", default="",
                     help="--deploy processes: pin the worker and the master to CPUs "
@@ -247,8 +264,8 @@ def main() -> int:
                     help="--deploy processes: an environment setting for both daemons (a GM_* "
                          "config override, e.g. GM_AUTHZ_SELF_REVIEW=false); repeatable")
     ap.add_argument("--call-cycles", type=int, default=5,
-                    help="after the timed loop: this many attach/detach cycles whose outbound "
-                         "apiserver/kubelet calls are read from the daemons' call logs "
+                    help="--full, after the timed loop: this many attach/detach cycles whose "
+                         "outbound apiserver/kubelet calls are read from the daemons' call logs "
                          "(serial_calls_per_attach / _detach); 0 = skip")
     ap.add_argument("--gpu-api", choices=("device-plugin", "dra"), default="device-plugin",
                     help="dra: the node's GPUs come from a DRA driver; placeholders hold "
@@ -276,7 +293,7 @@ def main() -> int:
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     n = args.gpus
     box = None
-    if rank == 0 and not args.no_calib:
+    if rank == 0 and args.full and not args.no_calib:
         # the box's speed next to the value (gpumounter_amd/utils/calib.py): before anything
         # initialises the GPU, since the calibration forks and spawns
         from gpumounter_amd.utils import calib
@@ -408,6 +425,7 @@ def main() -> int:
     samples = [] if args.dump_samples and rank == 0 else None
     first_attach = []    # the first attach after the daemons started (cold everything)
     first_stages = {}    # ... and where its time went
+    last_out = {}        # what the last step returned to its caller (--dump-outputs)
 
     def one_step(record: bool):
         nonlocal audit_issues, nccl_group
@@ -445,6 +463,7 @@ def main() -> int:
             dist.broadcast_object_list(obj, src=0)
         st = obj[0]
         last_bdfs[:] = st["bdfs"]
+        verified = 0
         if has_gpu and not args.no_verify:
             bdfs = sorted(st["bdfs"])           # stable rank → attached-GPU mapping
             # one process per GPU: each rank checks its own; a single process checks them all
@@ -454,6 +473,7 @@ def main() -> int:
                 if dev < 0:
                     raise RuntimeError(f"rank {rank}: attached GPU {mine} not visible to HIP")
                 us = probe.quick(dev)
+                verified += 1
                 if record:
                     probe_us.append(us)
                     probe_by_gpu.setdefault(mine, []).append(us)
@@ -492,6 +512,9 @@ def main() -> int:
             if args.warm_pool:   # steady state: the next attach finds a full pool
                 cp.wait_pool(min(args.warm_pool, pool_cap))
             if record:
+                last_out.update(attach_status=[200, code], audit_issues=[st["issues"]],
+                                attached_gpus=sorted(node_bdfs.index(b) for b in st["bdfs"]),
+                                gpus_verified=[1] * verified)
                 attach_ms.append(st["ms"])
                 if st.get("master_ms") is not None and st.get("worker_ms") is not None:
                     hop_ms.append((st["master_ms"], st["worker_ms"]))
@@ -554,7 +577,7 @@ def main() -> int:
             att = {gpu_by_bdf[b].index: gpu_by_bdf[b] for b in last_bdfs if b in gpu_by_bdf}
             _, att_hives, att_numa, att_nx = topology.score_set(att, link_matrix, sorted(att))
             p2p = None
-            if has_gpu and not args.no_verify and len(last_bdfs) > 1:
+            if args.full and has_gpu and not args.no_verify and len(last_bdfs) > 1:
                 devs = [probe.find_device(b) for b in sorted(last_bdfs)]
                 pairs = [probe.p2p(a, b, 64 << 20, 3) for a in devs for b in devs if a != b]
                 p2p = {"pairs": len(pairs),
@@ -562,8 +585,8 @@ def main() -> int:
                        "min_gbps": round(min(x["gbps"] for x in pairs), 1),
                        "max_gbps": round(max(x["gbps"] for x in pairs), 1)}
             tenant_view = tenant_view_pt = None
-            if has_gpu and not args.no_verify and args.node_ops == "emulated" and \
-                    args.protocol == "gpumounter" and args.cgroup == "v2":
+            if args.full and has_gpu and not args.no_verify and args.node_ops == "emulated" \
+                    and args.protocol == "gpumounter" and args.cgroup == "v2":
                 # BASELINE config "the Pod sees it", from a fresh tenant-side HIP process
                 from gpumounter_amd.ops import tenant
                 root, cg = cp.tenant_view()
@@ -601,7 +624,7 @@ def main() -> int:
             # by kind, and how many of them are serial (a real cluster charges each serial round
             # trip a millisecond or more; gpumounter_amd/utils/calls.py)
             accounting = None
-            if args.protocol == "gpumounter" and args.call_cycles > 0:
+            if args.full and args.protocol == "gpumounter" and args.call_cycles > 0:
                 acc = {"attach": [], "detach": []}
                 waits = []
                 for i in range(args.call_cycles):
@@ -632,7 +655,7 @@ def main() -> int:
                 accounting["attach"]["admission_wait_p50_ms"] = round(pct(w, 0.5), 4) \
                     if w else None
             cold = None
-            if args.cold_steps > 0 and args.protocol == "gpumounter":
+            if args.full and args.cold_steps > 0 and args.protocol == "gpumounter":
                 # the attach an operator makes minutes after the last one: every cached authz
                 # answer expired (the pod index is a watch, so it stays current). Two kinds of
                 # cold cycle, interleaved A B A B on the same master process (round 5 ran all A
@@ -692,20 +715,27 @@ def main() -> int:
                 else:        # one process, no authz (LocalCluster): idling alone
                     cold = {"steps": args.cold_steps, "idle_s": args.idle_s,
                             "authz": None, **idle_only, "idle_only": idle_only}
-            orphan_issues = len(cp.audit()) if args.protocol == "gpumounter" else None
-            corrections = cp.corrections() if args.protocol == "gpumounter" else None
-            refusals = cp.admission_refusals() if args.protocol == "gpumounter" else None
-            placeholders_left = cp.placeholders_left()
-            kcalls = cp.kubelet_calls()
+            checked = args.full and args.protocol == "gpumounter"
+            orphan_issues = len(cp.audit()) if checked else None
+            corrections = cp.corrections() if checked else None
+            refusals = cp.admission_refusals() if checked else None
+            placeholders_left = cp.placeholders_left() if args.full else None
+            kcalls = cp.kubelet_calls() if args.full else None
             p50 = pct(attach_ms, 0.5)
+            if args.dump_outputs:
+                import numpy as np
+                os.makedirs(args.dump_outputs, exist_ok=True)
+                for name, vals in last_out.items():
+                    np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                            np.asarray(vals, dtype=np.float64))
             ref = None
-            if args.ref_steps > 0 and args.node_ops == "real":
+            if args.full and args.ref_steps > 0 and args.node_ops == "real":
                 # the reference writes cgroup-v1 devices.allow/deny through `sh -c echo`
                 # (pkg/util/cgroup/cgroup.go:143-169); the real-node sandbox is cgroup2, which
                 # has no such files, so there is nothing faithful to re-enact here
                 ref = {"skipped": "the reference's node operations are cgroup-v1 only "
                                   "(devices.allow via sh); --node-ops real runs on cgroup2"}
-            elif args.ref_steps > 0 and args.protocol == "gpumounter" and \
+            elif args.full and args.ref_steps > 0 and args.protocol == "gpumounter" and \
                     args.latency == "zero" and not args.warm_pool:
                 # the reference's call sequence, emulated in the same deployment shape
                 # The reference dials the kubelet and Lists on every query with no retry
@@ -843,7 +873,8 @@ def main() -> int:
                 # PodResources traffic of this run against the limited kubelet (100 qps,
                 # burst 10): rejected calls were retried by the ledger client
                 "kubelet_calls": {k: kcalls.get(k, 0) for k in
-                                  ("List", "Get", "GetAllocatableResources", "rejected")},
+                                  ("List", "Get", "GetAllocatableResources", "rejected")}
+                if kcalls is not None else None,
                 "placeholders_left": placeholders_left,
                 # collections in this (client) process that paused it ≥ 5 ms: [generation, ms]
                 "client_gc_pauses": [list(x) for x in runtime.gc_pauses],

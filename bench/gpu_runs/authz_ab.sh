@@ -8,7 +8,7 @@ mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
 run() {   # name, bench args...
     local name=$1; shift
-    timeout -k 10 300 python bench.py --gpus 1 "$@" > "$O/$name.json" 2>> "$O/bench.err" \
+    timeout -k 10 300 python bench.py --full --gpus 1 "$@" > "$O/$name.json" 2>> "$O/bench.err" \
         || fail "$O/bench.err"
     python - "$O/$name.json" "$name" <<'PY'
 import json, sys

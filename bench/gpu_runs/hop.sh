@@ -16,13 +16,13 @@ GM_RECORD_MAPS="$O/maps_smoke.txt" timeout -k 10 300 python -c "import __graft_e
     > "$O/smoke.log" 2>&1 || fail "$O/smoke.log"
 tail -1 "$O/smoke.log"
 for i in 1 2 3; do
-    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench$i.json" \
+    timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench$i.json" \
         2>> "$O/bench.err" || fail "$O/bench.err"
     python -c "import json,sys; q=json.load(open('$O/bench$i.json')); print('bench', q['value'], q['attach_split_p50_ms'], q['detach_p50_ms'], q['cold_attach_p50_ms'], q['first_attach_ms'])"
 done
 mkdir -p "$O/prof"
 GM_PROFILE_OUT="$PWD/$O/prof/{pid}.json" GM_PROFILE_MODE=sample timeout -k 10 600 \
-    python bench.py --gpus 1 --steps 3000 --warmup 50 --cold-steps 0 \
+    python bench.py --full --gpus 1 --steps 3000 --warmup 50 --cold-steps 0 \
     --dump-samples "$O/soak.jsonl" > "$O/soak.json" 2>> "$O/bench.err" || fail "$O/bench.err"
 python bench/tail_report.py "$O/soak.jsonl" > "$O/tail_report.json" || true
 gzip -f "$O/soak.jsonl"

@@ -9,7 +9,7 @@ TAG=${1:-hops}
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$O"
 for i in 1 2 3; do
-    timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 \
+    timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 \
         --dump-samples "$O/b$i.samples.jsonl" > "$O/b$i.json" 2> "$O/b$i.err" || { tail -30 "$O/b$i.err"; exit 1; }
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['value'], d['attach_split_p50_ms'], d['master_stage_p50_ms'], {k: v for k, v in d['stage_p50_ms'].items() if k.startswith('rpc')}, d['box'])" "$O/b$i.json"
 done

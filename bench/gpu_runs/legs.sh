@@ -9,7 +9,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$O"
 run() {   # name, extra env assignments...
     n=$1; shift
-    env "$@" timeout -k 10 300 python3 bench.py --gpus 1 --steps 200 --warmup 20 --cold-steps 0 \
+    env "$@" timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 200 --warmup 20 --cold-steps 0 \
         --no-calib --dump-samples "$O/$n.jsonl" > "$O/$n.json" 2> "$O/$n.err" || { tail -30 "$O/$n.err"; exit 1; }
     python3 - "$O/$n.json" "$n" <<'PY'
 import json, sys
@@ -24,6 +24,6 @@ run base GM_X=0
 run no_events GM_EMIT_EVENTS=false
 run no_guard GM_DEVICE_GUARD_PERIOD_S=0
 run base2 GM_X=0
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 200 --warmup 20 --cold-steps 0 --no-calib \
+timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 200 --warmup 20 --cold-steps 0 --no-calib \
     --security off > "$O/insecure.json" 2> "$O/insecure.err" || { tail -30 "$O/insecure.err"; exit 1; }
 python3 -c "import json,sys; d=json.load(open(sys.argv[1])); m=d['master_stage_p50_ms']; print('insecure', d['value'], d['attach_split_p50_ms'], m.get('master_rpc.grpc_request'), m.get('master_rpc.grpc_response'))" "$O/insecure.json"

@@ -10,7 +10,7 @@ mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
 run() {   # name, bench args...
     local name=$1; shift
-    timeout -k 10 300 python bench.py --gpus 1 "$@" > "$O/$name.json" 2>> "$O/bench.err" \
+    timeout -k 10 300 python bench.py --full --gpus 1 "$@" > "$O/$name.json" 2>> "$O/bench.err" \
         || fail "$O/bench.err"
     python -c "import json; q=json.load(open('$O/$name.json')); a=q.get('serial_calls_per_attach') or {}; c=q.get('cold_attach') or {}; print('$name', q['value'], q['detach_p50_ms'], 'serial', a.get('serial_round_trips'), 'adm', a.get('admission_wait_p50_ms'), 'cold', q.get('cold_attach_p50_ms'), 'idle', (c.get('idle_only') or {}).get('attach_p50_ms'), 'first', q.get('first_attach_ms'))"
 }

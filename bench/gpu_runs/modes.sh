@@ -9,7 +9,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$O"
 run() {
     name=$1; shift
-    timeout -k 10 300 python bench.py --gpus 1 --steps 100 --warmup 20 --cold-steps 0 "$@" \
+    timeout -k 10 300 python bench.py --full --gpus 1 --steps 100 --warmup 20 --cold-steps 0 "$@" \
         > "$O/$name.json" 2> "$O/$name.err" || { tail -20 "$O/$name.err"; exit 1; }
     python - "$O/$name.json" "$name" <<'PY'
 import json, sys

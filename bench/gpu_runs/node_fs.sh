@@ -9,7 +9,7 @@ fail() { tail -40 "$1"; exit 1; }
 df -T /tmp /dev/shm "$GRAFT_REPO_ROOT" > "$O/df.txt" 2>&1 || true
 for i in 1 2; do
   for fs in disk tmpfs; do
-    timeout -k 10 300 python bench.py --steps 200 --warmup 20 --kernel-fs $fs \
+    timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 --kernel-fs $fs \
         > "$O/${fs}_$i.json" 2> "$O/${fs}_$i.err" || fail "$O/${fs}_$i.err"
   done
 done

@@ -20,7 +20,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke
     || fail "$O/smoke.log"
 tail -1 "$O/smoke.log"
 for i in 1 2 3; do
-    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 \
+    timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 \
         --dump-samples "$O/bench$i.jsonl" > "$O/bench$i.json" 2> "$O/bench$i.err" || fail "$O/bench$i.err"
     python - "$O/bench$i.json" <<'PY'
 import json, sys
@@ -34,7 +34,7 @@ for o in "" "--http" "--http --shield" "--http --big" "--http --retry" "--http -
          "--http --tls --retry --big --shield"; do
     timeout -k 10 120 python bench/gpu_runs/hop_floor.py $o | tee -a "$O/hop_floor.jsonl" || exit 1
 done
-timeout -k 10 400 python bench.py --gpus 1 --steps 3000 --warmup 50 --cold-steps 0 \
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 3000 --warmup 50 --cold-steps 0 \
     --dump-samples "$O/soak.jsonl" > "$O/soak.json" 2> "$O/soak.err" || fail "$O/soak.err"
 python bench/tail_report.py "$O/soak.jsonl" > "$O/tail_report.json"
 python - "$O/tail_report.json" <<'PY'
@@ -42,8 +42,9 @@ import json, sys
 r = json.load(open(sys.argv[1]))[0]
 print("soak", r["attach_ms"], "tail excess", dict(list(r["tail_excess_over_p50_ms"].items())[:5]))
 PY
+ROOT=$PWD   # the repository root: the profiler below runs from another directory
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --marker-trace --kernel-trace --stats -f csv -d "$O/rocprof" -o bench \
-    -- python3 "$GRAFT_REPO_ROOT/bench.py" --deploy inprocess --steps 50 --warmup 10 --cold-steps 0 \
+    -- python3 "$ROOT/bench.py" --full --deploy inprocess --steps 50 --warmup 10 --cold-steps 0 \
     > "$O/rocprof.log" 2>&1 || fail "$O/rocprof.log"
 echo rocprof-ok

@@ -13,16 +13,16 @@ O=gpurun_out/$TAG
 mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
 for i in 1 2; do
-    timeout -k 10 300 python bench.py > "$O/default_$i.json" 2> "$O/default_$i.err" \
+    timeout -k 10 300 python bench.py --full > "$O/default_$i.json" 2> "$O/default_$i.err" \
         || fail "$O/default_$i.err"
 done
-timeout -k 10 300 python bench.py --gpus 1 --steps 100 --warmup 20 --warm-pool 1 \
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 100 --warmup 20 --warm-pool 1 \
     > "$O/pool_floor.json" 2> "$O/pool_floor.err" || fail "$O/pool_floor.err"
-timeout -k 10 300 python bench.py --gpus 1 --steps 100 --warmup 20 --warm-pool 1 \
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 100 --warmup 20 --warm-pool 1 \
     --daemon-env GM_POOL_PRIORITY_CLASS=gpumounter-standby \
     > "$O/pool_low.json" 2> "$O/pool_low.err" || fail "$O/pool_low.err"
 for n in 1 2 4 8; do
-    timeout -k 10 240 python bench.py --amdsmi mock --gpus $n --steps 100 --warmup 20 \
+    timeout -k 10 240 python bench.py --full --amdsmi mock --gpus $n --steps 100 --warmup 20 \
         --cold-steps 0 > "$O/mock_n$n.json" 2> "$O/mock_n$n.err" || fail "$O/mock_n$n.err"
 done
 python - "$O" <<'PY'

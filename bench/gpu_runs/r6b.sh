@@ -11,10 +11,10 @@ O=gpurun_out/${1:-r6b}
 mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
 for i in 1 2 3; do
-    timeout -k 10 300 python bench.py > "$O/default_$i.json" 2> "$O/default_$i.err" \
+    timeout -k 10 300 python bench.py --full > "$O/default_$i.json" 2> "$O/default_$i.err" \
         || fail "$O/default_$i.err"
 done
-timeout -k 10 300 python bench.py --gpus 1 --steps 3000 --warmup 50 --cold-steps 0 \
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 3000 --warmup 50 --cold-steps 0 \
     --call-cycles 0 > "$O/soak3000.json" 2> "$O/soak3000.err" || fail "$O/soak3000.err"
 for m in default pool_floor pool_low; do
     case $m in
@@ -22,7 +22,7 @@ for m in default pool_floor pool_low; do
         pool_floor) extra="--warm-pool 1" ;;
         pool_low) extra="--warm-pool 1 --daemon-env GM_POOL_PRIORITY_CLASS=gpumounter-standby" ;;
     esac
-    timeout -k 10 300 python bench.py --gpus 1 --steps 10 --warmup 3 --cold-steps 0 \
+    timeout -k 10 300 python bench.py --full --gpus 1 --steps 10 --warmup 3 --cold-steps 0 \
         --latency realistic --no-verify $extra > "$O/model_$m.json" 2> "$O/model_$m.err" \
         || fail "$O/model_$m.err"
 done

@@ -7,11 +7,11 @@ O=gpurun_out/${1:-r6c}
 mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
 LOW="--daemon-env GM_POOL_PRIORITY_CLASS=gpumounter-standby"
-timeout -k 10 300 python bench.py --gpus 1 --steps 100 --warmup 20 --warm-pool 1 --cold-steps 0 \
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 100 --warmup 20 --warm-pool 1 --cold-steps 0 \
     > "$O/pool_floor.json" 2> "$O/pool_floor.err" || fail "$O/pool_floor.err"
-timeout -k 10 300 python bench.py --gpus 1 --steps 100 --warmup 20 --warm-pool 1 --cold-steps 0 \
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 100 --warmup 20 --warm-pool 1 --cold-steps 0 \
     $LOW > "$O/pool_low.json" 2> "$O/pool_low.err" || fail "$O/pool_low.err"
-timeout -k 10 300 python bench.py --gpus 1 --steps 10 --warmup 3 --cold-steps 0 \
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 10 --warmup 3 --cold-steps 0 \
     --latency realistic --no-verify --warm-pool 1 $LOW > "$O/model_pool_low.json" \
     2> "$O/model_pool_low.err" || fail "$O/model_pool_low.err"
 python - "$O" <<'PY'

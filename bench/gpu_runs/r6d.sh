@@ -14,11 +14,11 @@ for m in scheduler direct scheduler_pool direct_pool; do
         scheduler_pool) extra="--warm-pool 1" ;;
         direct_pool) extra="--warm-pool 1 --daemon-env GM_PLACEHOLDER_BINDING=direct" ;;
     esac
-    timeout -k 10 300 python bench.py --gpus 1 --steps 30 --warmup 3 --cold-steps 0 \
+    timeout -k 10 300 python bench.py --full --gpus 1 --steps 30 --warmup 3 --cold-steps 0 \
         --latency realistic --no-verify $extra > "$O/model_$m.json" 2> "$O/model_$m.err" \
         || fail "$O/model_$m.err"
 done
-timeout -k 10 300 python bench.py > "$O/default.json" 2> "$O/default.err" || fail "$O/default.err"
+timeout -k 10 300 python bench.py --full > "$O/default.json" 2> "$O/default.err" || fail "$O/default.err"
 python - "$O" <<'PY'
 import json, sys
 o = sys.argv[1]

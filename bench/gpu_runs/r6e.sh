@@ -24,7 +24,7 @@ for m in scheduler direct pool_floor pool_floor_direct pool_low pool_low_direct 
         mock8_direct) extra="--amdsmi mock $DIRECT" ;;
         mock8_pool_low) extra="--amdsmi mock --warm-pool 1 $LOW" ;;
     esac
-    timeout -k 10 300 python bench.py --gpus 1 --steps 30 --warmup 3 --cold-steps 0 \
+    timeout -k 10 300 python bench.py --full --gpus 1 --steps 30 --warmup 3 --cold-steps 0 \
         --latency realistic --no-verify $extra > "$O/model_$m.json" 2> "$O/model_$m.err" \
         || fail "$O/model_$m.err"
 done

@@ -8,13 +8,14 @@ TAG=${1:-rocprof}
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
+ROOT=$PWD   # the repository root: the profiler below runs from another directory
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --marker-trace --kernel-trace --stats -f csv -d "$O/inproc" -o bench \
-    -- python3 "$GRAFT_REPO_ROOT/bench.py" --deploy inprocess --steps 50 --warmup 10 --cold-steps 0 \
+    -- python3 "$ROOT/bench.py" --full --deploy inprocess --steps 50 --warmup 10 --cold-steps 0 \
     --call-cycles 0 > "$O/inproc.log" 2>&1 || fail "$O/inproc.log"
 echo inproc-ok
 timeout -k 10 300 rocprofv3 --marker-trace --kernel-trace --stats -f csv -d "$O/procs" -o bench \
-    -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 50 --warmup 10 --cold-steps 0 --call-cycles 0 \
+    -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 10 --cold-steps 0 --call-cycles 0 \
     > "$O/procs.log" 2>&1 || fail "$O/procs.log"
 echo procs-ok
 find "$O" -name "*_stats.csv" | sort

@@ -9,10 +9,10 @@ O=gpurun_out/$TAG
 mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
 for n in 1 2 4 8; do
-    timeout -k 10 240 python bench.py --amdsmi mock --gpus $n --steps 100 --warmup 20 \
+    timeout -k 10 240 python bench.py --full --amdsmi mock --gpus $n --steps 100 --warmup 20 \
         > "$O/mock_n$n.json" 2> "$O/mock_n$n.err" || fail "$O/mock_n$n.err"
 done
-timeout -k 10 240 python bench.py --gpus 1 --steps 100 --warmup 20 > "$O/real_n1.json" \
+timeout -k 10 240 python bench.py --full --gpus 1 --steps 100 --warmup 20 > "$O/real_n1.json" \
     2> "$O/real_n1.err" || fail "$O/real_n1.err"
 python - "$O" <<'PY'
 import json, sys

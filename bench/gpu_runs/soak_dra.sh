@@ -8,11 +8,11 @@ TAG=${1:-soak_dra}
 O=gpurun_out/$TAG
 mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
-timeout -k 10 400 python bench.py --gpus 1 --steps 3000 --warmup 50 --gpu-api dra \
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 3000 --warmup 50 --gpu-api dra \
     > "$O/dra_3000.json" 2> "$O/dra_3000.err" || fail "$O/dra_3000.err"
-timeout -k 10 400 python bench.py --gpus 1 --steps 3000 --warmup 50 --gpu-api dra --warm-pool 1 \
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 3000 --warmup 50 --gpu-api dra --warm-pool 1 \
     > "$O/dra_pool_3000.json" 2> "$O/dra_pool_3000.err" || fail "$O/dra_pool_3000.err"
-timeout -k 10 300 python bench.py --gpus 1 --steps 500 --warmup 20 --ref-steps 0 \
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 500 --warmup 20 --ref-steps 0 \
     > "$O/default_500.json" 2> "$O/default_500.err" || fail "$O/default_500.err"
 python - "$O" <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ N=${2:-30000}
 mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
 for i in 1 2; do
-    timeout -k 10 400 python bench.py --gpus 1 --steps "$N" --warmup 100 --cold-steps 0 \
+    timeout -k 10 400 python bench.py --full --gpus 1 --steps "$N" --warmup 100 --cold-steps 0 \
         --dump-samples "$O/soak$i.jsonl" > "$O/soak$i.json" 2>> "$O/bench.err" || fail "$O/bench.err"
     python bench/tail_report.py "$O/soak$i.jsonl" > "$O/tail_report$i.json" || true
     gzip -f "$O/soak$i.jsonl"

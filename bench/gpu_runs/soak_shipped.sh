@@ -8,9 +8,9 @@ TAG=${1:-soak_shipped}
 O=gpurun_out/$TAG
 mkdir -p "$O"
 fail() { tail -40 "$1"; exit 1; }
-timeout -k 10 400 python bench.py --gpus 1 --steps 3000 --warmup 50 --ref-steps 0 \
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 3000 --warmup 50 --ref-steps 0 \
     > "$O/default_3000.json" 2> "$O/default_3000.err" || fail "$O/default_3000.err"
-timeout -k 10 400 python bench.py --gpus 1 --steps 3000 --warmup 50 --warm-pool 1 \
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 3000 --warmup 50 --warm-pool 1 \
     > "$O/pool_3000.json" 2> "$O/pool_3000.err" || fail "$O/pool_3000.err"
 python - "$O" <<'PY'
 import json, sys

@@ -13,7 +13,7 @@ GM_RECORD_MAPS="$O/maps_smoke.txt" timeout -k 10 300 python -c "import __graft_e
     > "$O/smoke.log" 2>&1 || fail "$O/smoke.log"
 tail -1 "$O/smoke.log"
 for i in 1 2 3; do
-    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench$i.json" \
+    timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench$i.json" \
         2>> "$O/bench.err" || fail "$O/bench.err"
     python - "$O/bench$i.json" <<'EOF'
 import json, sys

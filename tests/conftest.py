@@ -35,6 +35,21 @@ def mock_inventory():
     return Inventory("mock")
 
 
+@pytest.fixture
+def short_tmp():
+    """A directory with a short path, for unix sockets and device nodes. A socket's path holds
+    at most 107 characters (sun_path) and the node writer's little more, and pytest's tmp_path
+    under a deep TMPDIR leaves too few of them."""
+    import shutil
+    import tempfile
+
+    bases = [tempfile.gettempdir(), "/tmp", "/dev/shm"]
+    base = next((b for b in bases if len(b) <= 40 and os.access(b, os.W_OK)), bases[0])
+    d = tempfile.mkdtemp(prefix="gm-t-", dir=base)
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
 def has_gpu() -> bool:
     try:
         import torch

@@ -27,7 +27,7 @@ def _last_json(out):
 
 def test_bench_single_process_json_line():
     env = {**os.environ, "CUDA_VISIBLE_DEVICES": ""}
-    res = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "1",
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "1",
                           "--amdsmi", "mock"], cwd=ROOT, capture_output=True, text=True,
                          timeout=300, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -39,9 +39,44 @@ def test_bench_single_process_json_line():
     assert d["placeholders_left"] == 0
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full: --steps timed steps and the result line, nothing that takes runs of its own;
+    --dump-outputs writes the last step's outputs, identical from run to run."""
+    import numpy as np
+    env = {**os.environ, "CUDA_VISIBLE_DEVICES": ""}
+    dumps = []
+    for name in ("a", "b"):
+        res = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4",
+                              "--warmup", "1", "--amdsmi", "mock", "--dump-outputs",
+                              str(tmp_path / name), "--dump-samples",
+                              str(tmp_path / (name + ".jsonl"))], cwd=ROOT, capture_output=True,
+                             text=True, timeout=300, env=env)
+        assert res.returncode == 0, res.stderr[-3000:]
+        d = _last_json(res.stdout)
+        assert KEYS <= set(d)
+        assert d["metric"] == "p50_gpu_attach_latency_ms" and d["unit"] == "ms"
+        assert d["higher_is_better"] is False and d["dtype"] == "none"
+        assert d["steps"] == 4 and d["value"] > 0 and d["ms_per_step"] >= d["value"]
+        with open(tmp_path / (name + ".jsonl")) as fh:      # one line per timed step
+            assert len(fh.read().splitlines()) == 4
+        assert d["ledger_audit_issues"] == 0
+        for moved in ("box", "cold_attach", "serial_calls_per_attach", "tenant_view", "p2p",
+                      "final_orphans", "placeholders_left", "kubelet_calls",
+                      "reference_emulated_same_run"):
+            assert d[moved] is None, moved
+        dumps.append({f: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["attach_status.npy", "attached_gpus.npy",
+                                      "audit_issues.npy", "gpus_verified.npy"]
+    for f in a:
+        assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f]), f
+    assert a["attach_status.npy"].tolist() == [200.0, 200.0]
+    assert a["attached_gpus.npy"].shape == (1,) and a["audit_issues.npy"].tolist() == [0.0]
+
+
 def test_bench_with_daemons_as_separate_processes():
     env = {**os.environ, "CUDA_VISIBLE_DEVICES": ""}
-    res = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "1",
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "1",
                           "--amdsmi", "mock", "--deploy", "processes"], cwd=ROOT,
                          capture_output=True, text=True, timeout=300, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -56,7 +91,7 @@ def test_bench_dra_cluster_daemons():
     """--gpu-api dra: the daemons run with gpu_allocation=dra against the fake apiserver's
     resource.k8s.io/v1 (placeholders hold ResourceClaims)."""
     env = {**os.environ, "CUDA_VISIBLE_DEVICES": ""}
-    res = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "1",
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "1",
                           "--amdsmi", "mock", "--deploy", "processes", "--gpu-api", "dra"],
                          cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -102,8 +137,9 @@ def test_bench_single_process_eight_gpus_verifies_every_per_n_field():
     """`bench.py --gpus 8` without a launcher (what a driver may run): all 8 attached, a collective
     over 8 spawned rank processes (gloo here, RCCL on MI355X), one hive, no non-xGMI pair."""
     env = {**os.environ, "CUDA_VISIBLE_DEVICES": ""}
-    res = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "3", "--warmup",
-                          "1", "--amdsmi", "mock", "--deploy", "inprocess", "--ref-steps", "0"],
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "8", "--steps", "3",
+                          "--warmup", "1", "--amdsmi", "mock", "--deploy", "inprocess",
+                          "--ref-steps", "0"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _last_json(res.stdout)
@@ -130,7 +166,7 @@ def test_bench_real_node_ops_reports_stage_split():
     env = {**os.environ, "CUDA_VISIBLE_DEVICES": ""}
     # --ref-steps with real node ops: the reference column is skipped with its reason, never
     # a crash
-    res = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "2",
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "10", "--warmup", "2",
                           "--amdsmi", "mock", "--node-ops", "real", "--ref-steps", "5"],
                          cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     assert res.returncode == 0, res.stderr[-3000:]

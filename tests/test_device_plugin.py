@@ -113,13 +113,13 @@ def test_plugin_reregisters_after_kubelet_restart():
     run(body)
 
 
-def test_standalone_device_plugin_cli_serves_the_api(tmp_path):
+def test_standalone_device_plugin_cli_serves_the_api(short_tmp):
     """python -m gpumounter_amd device-plugin: the plugin without a worker."""
     import subprocess
     import sys
 
-    d = tmp_path / "dp"
-    d.mkdir()
+    d = os.path.join(short_tmp, "dp")
+    os.mkdir(d)
     proc = subprocess.Popen([sys.executable, "-m", "gpumounter_amd", "device-plugin",
                              "--amdsmi", "mock", "--dir", str(d), "--no-register"],
                             stdout=subprocess.PIPE, text=True,

@@ -168,10 +168,10 @@ def test_same_namespace_owner_gc_cascades(tmp_path, mock_inventory):
 
 # ----------------------------------------------------------------------------------- ledger
 @pytest.mark.parametrize("serve_v1", [True, False])
-def test_ledger_client_v1_and_v1alpha1_fallback(tmp_path, mock_inventory, serve_v1):
+def test_ledger_client_v1_and_v1alpha1_fallback(tmp_path, short_tmp, mock_inventory, serve_v1):
     async def run():
         node = FakeNode("n", str(tmp_path), mock_inventory.gpus(), mock_inventory.links())
-        sock = os.path.join(str(tmp_path), "kubelet.sock")
+        sock = os.path.join(short_tmp, "kubelet.sock")
         kl = FakeKubelet(node, sock, serve_v1=serve_v1, serve_v1alpha1=True)
         await kl.start()
         ids = node.allocate("gpu-pool", "p1", "c", 2)

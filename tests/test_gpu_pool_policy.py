@@ -60,9 +60,21 @@ def _is_ignored(rel, pats):
     return False
 
 
+def _tree_files():
+    try:
+        return subprocess.run(["git", "ls-files", "--cached", "--others", "--exclude-standard"],
+                              cwd=ROOT, capture_output=True, text=True, check=True).stdout.split()
+    except (OSError, subprocess.CalledProcessError):
+        # an exported tree, or a checkout that git refuses to read for this user: every file in it
+        out = []
+        for d, dirs, files in os.walk(ROOT):
+            dirs[:] = [x for x in dirs if x != ".git"]
+            out += [os.path.relpath(os.path.join(d, f), ROOT) for f in files]
+        return out
+
+
 def shipped_sources():
-    out = subprocess.run(["git", "ls-files", "--cached", "--others", "--exclude-standard"],
-                         cwd=ROOT, capture_output=True, text=True, check=True).stdout.split()
+    out = _tree_files()
     pats = _ignored()
     for rel in out:
         base = os.path.basename(rel)

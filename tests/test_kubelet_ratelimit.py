@@ -46,10 +46,10 @@ def test_token_bucket_allow_and_acquire():
         TokenBucket(0, 1)
 
 
-def test_client_retries_resource_exhausted(tmp_path):
+def test_client_retries_resource_exhausted(tmp_path, short_tmp):
     inv = Inventory("mock")
     node = FakeNode("n", str(tmp_path), inv.gpus())
-    sock = os.path.join(str(tmp_path), "pr", "kubelet.sock")
+    sock = os.path.join(short_tmp, "pr", "kubelet.sock")
 
     async def body():
         kl = FakeKubelet(node, sock, rate_limit=(20.0, 1))
@@ -66,10 +66,10 @@ def test_client_retries_resource_exhausted(tmp_path):
     assert rejected > 0 and throttled == rejected
 
 
-def test_paced_client_is_never_rejected(tmp_path):
+def test_paced_client_is_never_rejected(tmp_path, short_tmp):
     inv = Inventory("mock")
     node = FakeNode("n", str(tmp_path), inv.gpus())
-    sock = os.path.join(str(tmp_path), "pr", "kubelet.sock")
+    sock = os.path.join(short_tmp, "pr", "kubelet.sock")
 
     async def body():
         kl = FakeKubelet(node, sock)                  # the kubelet default: 100 qps, burst 10
@@ -119,12 +119,12 @@ def test_attach_reads_the_ledger_once_per_event():
     assert run(body) <= 4
 
 
-def test_count_mode_serves_and_counts_over_budget_calls(tmp_path):
+def test_count_mode_serves_and_counts_over_budget_calls(tmp_path, short_tmp):
     """limit_mode="count" (how bench.py times the emulated reference, which has no retry):
     every call is served, the ones a limited kubelet would reject are counted."""
     inv = Inventory("mock")
     node = FakeNode("n", str(tmp_path), inv.gpus())
-    sock = os.path.join(str(tmp_path), "pr", "kubelet.sock")
+    sock = os.path.join(short_tmp, "pr", "kubelet.sock")
 
     async def body():
         kl = FakeKubelet(node, sock, rate_limit=(20.0, 1), limit_mode="count")

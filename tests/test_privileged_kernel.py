@@ -295,10 +295,10 @@ def test_cgroup_v1_devices_controller():
         os.rmdir(cg)
 
 
-def test_devnodes_real_mknod_via_setns(tmp_path):
+def test_devnodes_real_mknod_via_setns(short_tmp):
     """procroot + setns modes against a real process in a private mount namespace."""
-    root = tmp_path / "ctr"
-    (root / "dev").mkdir(parents=True)
+    root = os.path.join(short_tmp, "ctr")
+    os.makedirs(os.path.join(root, "dev"))
     # a sleeper in a new mount namespace whose /dev is a private tmpfs
     child = subprocess.Popen(["unshare", "-m", "--propagation", "private", "sh", "-c",
                               f"mount -t tmpfs tmpfs {root}/dev && echo ok && sleep 60"],

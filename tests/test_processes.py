@@ -299,7 +299,13 @@ def test_one_nodes_worker_down_leaves_the_other_node_served():
         code, body = pc.add("default", "t0", 1)
         assert code == 500 and time.monotonic() - t < 30, (code, body)
         pc.restart_worker("node-0")
+        # restart_worker returns once the worker is registered with the apiserver; the master
+        # hears of it through its pod watch, one event later
+        t = time.monotonic()
         code, g = pc.pod_gpus("default", "t0")
+        while code == 500 and time.monotonic() - t < 5:
+            time.sleep(0.02)
+            code, g = pc.pod_gpus("default", "t0")
         assert code == 200 and [x["uuid"] for x in g["gpus"] if x["source"] == "hot-mount"] \
             == [d["uuid"] for d in b0["devices"]], g
         code, b2 = pc.add("default", "t0", 1)
