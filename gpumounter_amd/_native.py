@@ -217,6 +217,23 @@ class ProbeProps(C.Structure):
                 ("clock_khz", C.c_int32), ("mem_clock_khz", C.c_int32)]
 
 
+class MemtestRecord(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("expected", C.c_uint64), ("got", C.c_uint64),
+                ("pattern", C.c_uint32), ("pass_", C.c_uint32)]
+
+
+MEMTEST_MAX_RECORDS = 16      # native/include/gm_probe.h GM_MEMTEST_MAX_RECORDS
+
+
+class MemtestResult(C.Structure):
+    _fields_ = [("bytes_tested", C.c_uint64), ("words_in_error", C.c_uint64),
+                ("bit_errors", C.c_uint64), ("stuck_mask", C.c_uint64),
+                ("records_filled", C.c_uint32), ("allocations", C.c_uint32),
+                ("records", MemtestRecord * MEMTEST_MAX_RECORDS),
+                ("seconds", C.c_double), ("write_gbps", C.c_double),
+                ("read_gbps", C.c_double), ("rw_gbps", C.c_double)]
+
+
 def _prefer_torch_hip_runtime() -> None:
     """A process can hold only one HIP runtime, and ``libamdhip64.so.7`` is resolved by soname:
     whichever copy is loaded first (ROCm's /opt/rocm/lib or the one PyTorch bundles) serves
@@ -264,6 +281,18 @@ def probe() -> C.CDLL:
                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib.gm_probe_p2p.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int),
                                      C.POINTER(C.c_double)]
+        lib.gm_probe_mem_info.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        lib.gm_probe_memtest_expected.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64,
+                                                  C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.gm_probe_memtest_fill.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,
+                                              C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p]
+        lib.gm_probe_memtest_verify.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,
+                                                C.c_int, C.c_uint64, C.c_uint32, C.c_uint64,
+                                                C.c_void_p, C.POINTER(MemtestResult)]
+        lib.gm_probe_memtest.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
+                                         C.c_uint64, C.c_uint64, C.c_uint64,
+                                         C.POINTER(MemtestResult)]
+        lib.gm_probe_memtest_store_variant.argtypes = [C.c_int]
         lib.gm_probe_strerror.argtypes = [C.c_int]
         lib.gm_probe_strerror.restype = C.c_char_p
         lib._gm_typed = True

@@ -5,11 +5,15 @@
     python -m gpumounter_amd inventory [--amdsmi mock]          # amdsmi view of this node
     python -m gpumounter_amd topology  [--amdsmi mock] [-n 4]   # xGMI/NUMA placement preview
     python -m gpumounter_amd probe     [--bdf 0000:05:00.0] [--full] [--burn-in 60]  # gfx950 kernels
+                                       [--memtest [SIZE]] [--memtest-passes N]
+                                       [--memtest-patterns addr,solid,checker,walk,random]
+                                       [--memtest-flip OFFSET:MASK]          # HBM pattern test
     python -m gpumounter_amd add    --master URL --ns NS --pod P -n 2 [--entire] [--lease 3600]
     python -m gpumounter_amd remove --master URL --ns NS --pod P --uuid U [--uuid U2] [--force]
     python -m gpumounter_amd status --master URL --node NODE
     python -m gpumounter_amd bpf-dump --allow 226:128 --allow 511:0   # generated device program
     python -m gpumounter_amd doctor  [--json] [--skip-cluster] [--gpu [--burn-in 30]]  # preflight
+                                     [--gpu --memtest [SIZE]]
     python -m gpumounter_amd config-doc > docs/CONFIG.md   # every GM_* setting, from the source
 
 The reference ships only the two daemons and documents curl calls (QuickStart.md:41-92); the
@@ -143,6 +147,31 @@ def cmd_topology(args) -> int:
     return 0
 
 
+MEMTEST_AUTO = -1     # --memtest without a SIZE: most of the device's free memory
+
+
+def _memtest_bytes(size: int) -> Optional[int]:
+    return None if size == MEMTEST_AUTO else size
+
+
+def _memtest_arg(kind):
+    """argparse type for the --memtest-* options: the parser in ops.memtest, with its refusal
+    turned into a usage error."""
+    def conv(text):
+        from gpumounter_amd.ops import memtest
+        try:
+            return getattr(memtest, kind)(text)
+        except memtest.ProbeError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    conv.__name__ = kind
+    return conv
+
+
+def _add_memtest_size(p, what: str) -> None:
+    p.add_argument("--memtest", nargs="?", const=MEMTEST_AUTO, default=None, metavar="SIZE",
+                   type=_memtest_arg("parse_size"), help=what)
+
+
 def cmd_probe(args) -> int:
     from gpumounter_amd.ops import probe
 
@@ -156,6 +185,14 @@ def cmd_probe(args) -> int:
         for r in res:
             r["burn_in"] = probe.burn_in(r["device"], args.burn_in)
             bad |= not r["burn_in"]["ok"]
+    if args.memtest is not None:
+        from gpumounter_amd.ops import memtest
+
+        for r in res:
+            r["memtest"] = memtest.memtest(
+                r["device"], _memtest_bytes(args.memtest), patterns=args.memtest_patterns,
+                passes=args.memtest_passes, _flip=args.memtest_flip)
+            bad |= not r["memtest"]["ok"]
     print(json.dumps(res, indent=2))
     return 1 if bad else 0
 
@@ -309,8 +346,10 @@ def cmd_doctor(args) -> int:
     from gpumounter_amd.utils import doctor
 
     cfg = _cfg(args)
-    checks = doctor.run(cfg, skip_cluster=args.skip_cluster, gpu=args.gpu or bool(args.burn_in),
-                        burn_in_s=args.burn_in)
+    memtest_bytes = args.memtest if args.memtest is not None else 0   # negative: automatic size
+    checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
+                        gpu=args.gpu or bool(args.burn_in) or bool(memtest_bytes),
+                        burn_in_s=args.burn_in, memtest_bytes=memtest_bytes)
     print(doctor.render(checks, args.json))
     return 1 if any(c.status == "fail" for c in checks) else 0
 
@@ -347,6 +386,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--full", action="store_true")
     p.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
                    help="sustained GEMM load with bit-exact result checks (exit 1 on mismatch)")
+    _add_memtest_size(p, "HBM pattern test over SIZE bytes (64M, 8G; default: 90 %% of the free "
+                         "memory) of every probed GPU (exit 1 on any bad word)")
+    p.add_argument("--memtest-passes", type=int, default=1, metavar="N")
+    p.add_argument("--memtest-patterns", type=_memtest_arg("parse_patterns"),
+                   default=("addr", "solid", "checker", "walk", "random"), metavar="a,b,...")
+    p.add_argument("--memtest-flip", type=_memtest_arg("parse_flip"), default=None,
+                   metavar="OFFSET:MASK",
+                   help="negative control: corrupt that word after every fill; the test must fail")
     p.set_defaults(fn=cmd_probe)
     for name, fn in (("add", cmd_add), ("remove", cmd_remove), ("status", cmd_status)):
         p = sub.add_parser(name)
@@ -382,6 +429,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also run the gfx950 liveness kernel on every GPU")
     p.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
                    help="with --gpu: sustained bit-checked GEMM load per GPU")
+    _add_memtest_size(p, "with --gpu: HBM pattern test over SIZE bytes per GPU (default: 90 %% of "
+                         "its free memory)")
     p.set_defaults(fn=cmd_doctor)
     p = sub.add_parser("bpf-dump")
     p.add_argument("--allow", action="append", default=[])

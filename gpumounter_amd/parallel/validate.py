@@ -10,7 +10,10 @@ starting a job on them — the reference offers nothing here:
    (:func:`collectives.allreduce_check`);
 4. optionally (``--burn-in SECONDS``) all GPUs under sustained MFMA load at once, each
    result bit-compared with the first: bf16 GEMMs for SECONDS (:func:`probe.burn_in`). Catches
-   silent data corruption and throttling that a short probe misses.
+   silent data corruption and throttling that a short probe misses;
+5. optionally (``--memtest [SIZE]``) the HBM pattern test on all GPUs at once
+   (:func:`gpumounter_amd.ops.memtest.memtest`): SIZE bytes per GPU, by default 90 % of what is
+   free on it, written and read back in both polarities of five patterns.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -71,7 +74,17 @@ def main(argv=None) -> int:
     ap.add_argument("--no-p2p", action="store_true")
     ap.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
                     help="then load every GPU at once with bit-checked GEMMs for SECONDS")
+    ap.add_argument("--memtest", nargs="?", const="auto", default=None, metavar="SIZE",
+                    help="then the HBM pattern test on every GPU at once over SIZE bytes each "
+                         "(64M, 8G; default: 90 %% of the free memory)")
     args = ap.parse_args(argv)
+    memtest_bytes = None
+    if args.memtest not in (None, "auto"):
+        from gpumounter_amd.ops import memtest
+        try:
+            memtest_bytes = memtest.parse_size(args.memtest)
+        except memtest.ProbeError as e:
+            ap.error(str(e))
     report: Dict = {"ok": True}
     if args.cpu_ranks:
         world = args.cpu_ranks
@@ -108,6 +121,15 @@ def main(argv=None) -> int:
             burn = list(ex.map(lambda d: probe.burn_in(d, args.burn_in), range(world)))
         report["burn_in"] = burn
         report["ok"] &= all(b["ok"] for b in burn)
+    if args.memtest is not None and not args.cpu_ranks:
+        from concurrent.futures import ThreadPoolExecutor
+
+        from gpumounter_amd.ops import memtest
+
+        with ThreadPoolExecutor(max_workers=world) as ex:
+            mt = list(ex.map(lambda d: memtest.memtest(d, memtest_bytes), range(world)))
+        report["memtest"] = mt
+        report["ok"] &= all(m["ok"] for m in mt)
     print(json.dumps(report))
     return 0 if report["ok"] else 1
 

@@ -280,11 +280,13 @@ async def _check_priority(cfg, kube) -> List[Check]:
     return out
 
 
-def check_gpus(cfg, burn_in_s: float = 0.0) -> List[Check]:
+def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
+               memtest_flip=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
-    sustained bit-checked bf16 GEMM load per GPU. A GPU that fails here should not be handed
-    out."""
+    sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
+    test over that many bytes per GPU (negative: 90 % of what is free on it); ``memtest_flip``
+    = (offset, mask) is its negative control. A GPU that fails here should not be handed out."""
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import probe
 
@@ -316,6 +318,14 @@ def check_gpus(cfg, burn_in_s: float = 0.0) -> List[Check]:
                 detail += (f", burn-in {b['seconds']:g} s {b['tflops']:.0f} TF/s "
                            f"{b['mismatches']} mismatching words")
                 status = status if b["ok"] else "fail"
+            if memtest_bytes:
+                from gpumounter_amd.ops import memtest
+
+                m = memtest.memtest(d, memtest_bytes if memtest_bytes > 0 else None,
+                                    _flip=memtest_flip)
+                detail += (f", memtest {m['bytes'] / 2**30:.2f} GiB {m['read_gbps']:.0f} / "
+                           f"{m['write_gbps']:.0f} GB/s {m['errors']} bad words")
+                status = status if m["ok"] else "fail"
             out.append(Check(f"gpu{d}", status, detail))
         except Exception as e:  # noqa: BLE001 - a faulting GPU is exactly what this finds
             out.append(Check(f"gpu{d}", "fail", f"probe failed: {e}"))
@@ -326,11 +336,11 @@ def check_gpus(cfg, burn_in_s: float = 0.0) -> List[Check]:
 
 
 def run(cfg, skip_cluster: bool = False, gpu: bool = False,
-        burn_in_s: float = 0.0) -> List[Check]:
+        burn_in_s: float = 0.0, *, memtest_bytes: int = 0) -> List[Check]:
     checks = check_inventory(cfg) + check_cgroup(cfg) + check_devnodes(cfg) + \
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
-        checks += check_gpus(cfg, burn_in_s)
+        checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes)
     if not skip_cluster:
         async def both():
             return await _check_kubelet(cfg) + await _check_apiserver(cfg)

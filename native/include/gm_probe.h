@@ -69,6 +69,83 @@ int gm_probe_gemm_check(int dev, int M, int N, int K, double* max_abs_err, doubl
 int gm_probe_p2p(int dev_a, int dev_b, uint64_t bytes, int iters, int* can_access, double* gbps);
 const char* gm_probe_strerror(int err);
 
+// ------------------------------------------------------------------ HBM pattern test (memtest)
+// Free and total device memory of `dev` in bytes (hipMemGetInfo).
+int gm_probe_mem_info(int dev, uint64_t* free_bytes, uint64_t* total_bytes);
+
+// A test region is a logical range of bytes that may span several device allocations. Every
+// 64-bit word of it has an expected value that is a pure function of (pattern, seed, pass, o),
+// o = the word's global byte offset in the region (allocation base offset + local offset, a
+// uint64_t multiple of 8), w = o / 8, all arithmetic modulo 2^64 (2^32 where marked u32):
+//
+//   GM_MEMTEST_ADDR    1   o ^ seed                      a word holds its own address
+//   GM_MEMTEST_SOLID   2   0
+//   GM_MEMTEST_CHECKER 4   0x5555555555555555
+//   GM_MEMTEST_WALK    8   1 << ((w + pass) & 63)
+//   GM_MEMTEST_RANDOM  16  v = w ^ seed ^ ((u64)(u32)(pass * 0x9E3779B9) << 32)
+//                          x = (u32)v, y = (u32)(v >> 32)
+//                          for c in 0x9E3779B9, 0x85EBCA6B, 0xC2B2AE35, 0x27D4EB2F:
+//                            x = (u32)(rotl32(x, 24) + y) ^ c
+//                            y = rotl32(y, 3) ^ x
+//                          value = ((u64)y << 32) | x
+//
+// The inverted polarity of a pattern is the bitwise NOT of the value. The code is
+// gm_memtest_pattern.h (shared by the host and the kernels).
+typedef struct gm_memtest_record {
+  uint64_t offset;    // global byte offset of the word in the region
+  uint64_t expected;
+  uint64_t got;
+  uint32_t pattern;   // GM_MEMTEST_* bit
+  uint32_t pass;
+} gm_memtest_record_t;
+
+#define GM_MEMTEST_MAX_RECORDS 16
+
+typedef struct gm_memtest_result {
+  uint64_t bytes_tested;
+  uint64_t words_in_error;  // 64-bit words that differed, summed over every verify
+  uint64_t bit_errors;      // sum of popcount(expected ^ got)
+  uint64_t stuck_mask;      // OR of expected ^ got
+  uint32_t records_filled;  // <= GM_MEMTEST_MAX_RECORDS; later mismatches are counted only
+  uint32_t allocations;     // device allocations the driver used (0 for caller-owned buffers)
+  gm_memtest_record_t records[GM_MEMTEST_MAX_RECORDS];
+  double seconds;           // wall time of the whole call
+  double write_gbps;        // bytes written by the fill kernels / their time
+  double read_gbps;         // bytes read by the verify-only kernels / their time
+  double rw_gbps;           // bytes read + written by verify-and-invert / its time
+} gm_memtest_result_t;
+
+// Host-side evaluation of the pattern function: out[i] = value of the word at byte offset
+// base_offset + 8 i. Needs no GPU. base_offset % 8 == 0, pattern one GM_MEMTEST_* bit.
+int gm_probe_memtest_expected(uint32_t pattern, uint64_t seed, uint32_t pass,
+                              uint64_t base_offset, uint64_t n_words, uint64_t* out);
+// Fill / check a caller-owned device buffer on the current device. `ptr` 16-byte aligned,
+// `bytes` a nonzero multiple of 16, `base_offset` a multiple of 8, `pattern` one GM_MEMTEST_*
+// bit: anything else is hipErrorInvalidValue before any HIP call. `invert` selects ~P.
+// Both are asynchronous on `stream` (may be NULL) except that verify waits for its result.
+int gm_probe_memtest_fill(void* ptr, uint64_t bytes, uint32_t pattern, int invert, uint64_t seed,
+                          uint32_t pass, uint64_t base_offset, void* stream);
+// With `write_inverse` the same kernel also writes the opposite polarity over every word it has
+// read (whatever it read there). Only the error fields and bytes_tested of *out are set.
+int gm_probe_memtest_verify(void* ptr, uint64_t bytes, uint32_t pattern, int invert,
+                            int write_inverse, uint64_t seed, uint32_t pass,
+                            uint64_t base_offset, void* stream, gm_memtest_result_t* out);
+// The self-contained test of `bytes` (multiple of 16) of device memory on `dev`, allocated in
+// pieces of at most `chunk_bytes` (0 = 8 GiB, else a multiple of 16). For each pattern of
+// `pattern_mask` and each of `passes`: fill(P), verify P while writing ~P, verify ~P, every kernel
+// over the whole region in the same order. A failed allocation is retried at half the size (not
+// below min(256 MiB, its size)); if that fails too, the test runs on what it has and
+// out->bytes_tested says how much; the HIP error is returned only if nothing could be allocated.
+// flip_mask != 0 is the negative control: after every fill(P) the word at global byte offset
+// flip_offset (multiple of 8, inside `bytes`) is XORed with flip_mask through a host round trip;
+// it is skipped if the offset lies beyond what could be allocated.
+int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pattern_mask,
+                     int passes, uint64_t seed, uint64_t flip_offset, uint64_t flip_mask,
+                     gm_memtest_result_t* out);
+// Tuning hook: 1 = nontemporal stores in fill and verify-and-invert (default), 0 = plain stores.
+// Returns the previous setting; any other value only queries.
+int gm_probe_memtest_store_variant(int nontemporal);
+
 #ifdef __cplusplus
 }
 #endif
