@@ -264,6 +264,8 @@ def probe() -> C.CDLL:
         lib.gm_probe_find_device.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
         lib.gm_probe_quick.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         lib.gm_probe_hbm_copy.argtypes = [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_double)]
+        lib.gm_probe_hbm_copy_variant.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int,
+                                                  C.POINTER(C.c_double)]
         lib.gm_probe_hbm_read.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int,
                                           C.POINTER(C.c_double)]
         lib.gm_probe_mfma_peak.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
@@ -277,6 +279,16 @@ def probe() -> C.CDLL:
                                                 C.POINTER(C.c_double)]
         lib.gm_probe_burn_in.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double),
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        lib.gm_probe_burn_in_flip.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int,
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint16),
+                                              C.POINTER(C.c_double), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_int)]
+        lib.gm_probe_count_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                            C.POINTER(C.c_uint64)]
+        lib.gm_probe_fill_bf16.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+        lib.gm_probe_copy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                                      C.c_void_p]
+        lib.gm_probe_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
         lib.gm_probe_gemm_check.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib.gm_probe_p2p.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int),

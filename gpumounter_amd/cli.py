@@ -5,6 +5,7 @@
     python -m gpumounter_amd inventory [--amdsmi mock]          # amdsmi view of this node
     python -m gpumounter_amd topology  [--amdsmi mock] [-n 4]   # xGMI/NUMA placement preview
     python -m gpumounter_amd probe     [--bdf 0000:05:00.0] [--full] [--burn-in 60]  # gfx950 kernels
+                                       [--burn-in-flip ELEM:MASK]            # its negative control
                                        [--memtest [SIZE]] [--memtest-passes N]
                                        [--memtest-patterns addr,solid,checker,walk,random]
                                        [--memtest-flip OFFSET:MASK]          # HBM pattern test
@@ -167,6 +168,15 @@ def _memtest_arg(kind):
     return conv
 
 
+def _burn_in_flip(text):
+    """argparse type for --burn-in-flip: the parser in ops.probe, its refusal a usage error."""
+    from gpumounter_amd.ops import probe
+    try:
+        return probe.parse_burn_in_flip(text)
+    except probe.ProbeError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def _add_memtest_size(p, what: str) -> None:
     p.add_argument("--memtest", nargs="?", const=MEMTEST_AUTO, default=None, metavar="SIZE",
                    type=_memtest_arg("parse_size"), help=what)
@@ -175,6 +185,9 @@ def _add_memtest_size(p, what: str) -> None:
 def cmd_probe(args) -> int:
     from gpumounter_amd.ops import probe
 
+    if args.burn_in_flip and not args.burn_in:
+        print("probe: --burn-in-flip needs --burn-in SECONDS", file=sys.stderr)
+        return 2                      # a usage error, not a failed burn-in (exit 1)
     if args.bdf:
         bdfs = args.bdf
     else:
@@ -183,7 +196,7 @@ def cmd_probe(args) -> int:
     bad = False
     if args.burn_in:
         for r in res:
-            r["burn_in"] = probe.burn_in(r["device"], args.burn_in)
+            r["burn_in"] = probe.burn_in(r["device"], args.burn_in, _flips=args.burn_in_flip)
             bad |= not r["burn_in"]["ok"]
     if args.memtest is not None:
         from gpumounter_amd.ops import memtest
@@ -386,6 +399,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--full", action="store_true")
     p.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
                    help="sustained GEMM load with bit-exact result checks (exit 1 on mismatch)")
+    p.add_argument("--burn-in-flip", type=_burn_in_flip, action="append", default=None,
+                   metavar="ELEM:MASK",
+                   help="negative control (repeatable): XOR that bf16 element of the burn-in's "
+                        "reference result with MASK; the burn-in must fail")
     _add_memtest_size(p, "HBM pattern test over SIZE bytes (64M, 8G; default: 90 %% of the free "
                          "memory) of every probed GPU (exit 1 on any bad word)")
     p.add_argument("--memtest-passes", type=int, default=1, metavar="N")

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import asdict, dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence, Tuple
 
 from gpumounter_amd import _native
 
@@ -142,23 +142,147 @@ def gemm_nt(a, bt, out=None, stream=None, variant: Optional[int] = None):
 
 
 def gemm_tflops(dev: int, m: int = 8192, n: int = 8192, k: int = 8192, iters: int = 10) -> float:
-    """Dense bf16 TF/s of the 256²-tile GEMM on uniform [-1,1) operands (burn-in load)."""
+    """Dense bf16 TF/s of the 256²-tile GEMM on uniform [-1,1] operands (burn-in load)."""
     t = C.c_double(0)
     _check(_native.probe().gm_probe_gemm_nt_tflops(dev, m, n, k, iters, C.byref(t)),
            "gemm tflops")
     return t.value
 
 
-def burn_in(dev: int, seconds: float = 10.0, n: int = 8192) -> Dict:
+def parse_burn_in_flip(text) -> Tuple[int, int]:
+    """``"ELEM:MASK"`` (any Python integer literal, e.g. ``8:0x8000``) → (element, mask): a bf16
+    element index of the burn-in's reference result and a nonzero 16-bit XOR mask."""
+    try:
+        elem, mask = str(text).split(":")
+        elem, mask = int(elem, 0), int(mask, 0)
+    except ValueError:
+        raise ProbeError(f"burn-in: cannot read {text!r} as ELEM:MASK") from None
+    if elem < 0 or not 0 < mask < 1 << 16:
+        raise ProbeError(f"burn-in: flip {text!r} needs ELEM >= 0 and 0 < MASK < 0x10000")
+    return elem, mask
+
+
+def burn_in(dev: int, seconds: float = 10.0, n: int = 8192,
+            _flips: Optional[Sequence[Tuple[int, int]]] = None) -> Dict:
     """Sustained-load check of an attached GPU: back-to-back n³ bf16 GEMMs for ``seconds``,
     each compared bit-for-bit with the first result (the kernel is deterministic). Any
     ``mismatches`` means silent data corruption. ``tflops`` is the sustained rate, so
-    throttling shows up as a low number."""
+    throttling shows up as a low number. ``_flips=[(elem, mask), ...]`` is the negative control:
+    those bf16 elements of the reference result are XORed with ``mask`` before the loop, so
+    every iteration must count each 16-byte word they touch."""
+    flips = list(_flips or ())
+    elems = [e for e, _ in flips]
+    for e, m in flips:
+        if not (isinstance(e, int) and isinstance(m, int) and 0 <= e < n * n and 0 < m < 1 << 16):
+            raise ProbeError(f"burn-in: flip ({e!r}, {m!r}) needs 0 <= elem < n*n and a nonzero "
+                             f"16-bit mask")
+    if len(set(elems)) != len(elems):
+        raise ProbeError("burn-in: an element may be flipped only once")
+    fe = (C.c_uint64 * max(1, len(flips)))(*elems)
+    fm = (C.c_uint16 * max(1, len(flips)))(*[m for _, m in flips])
     tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
-    _check(_native.probe().gm_probe_burn_in(dev, n, seconds, C.byref(tf), C.byref(bad),
-                                            C.byref(it)), "burn-in")
-    return {"device": dev, "n": n, "seconds": seconds, "iterations": it.value,
-            "tflops": tf.value, "mismatches": bad.value, "ok": bad.value == 0}
+    _check(_native.probe().gm_probe_burn_in_flip(dev, n, seconds, len(flips), fe, fm,
+                                                 C.byref(tf), C.byref(bad), C.byref(it)),
+           "burn-in")
+    out = {"device": dev, "n": n, "seconds": seconds, "iterations": it.value,
+           "tflops": tf.value, "mismatches": bad.value, "ok": bad.value == 0}
+    if flips:
+        out["flipped_words"] = len({e // 8 for e in elems})
+    return out
+
+
+def _dev_bytes(t, what: str, align: int = 16, multiple: int = 16) -> int:
+    """Checks a tensor a stream kernel may walk as raw bytes; returns its size in bytes."""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise ProbeError(f"{what} expects a torch tensor")
+    if t.device.type != "cuda":
+        raise ProbeError(f"{what} expects a tensor on a HIP device, got {t.device}")
+    if not t.is_contiguous():
+        raise ProbeError(f"{what} expects a contiguous tensor")
+    nbytes = t.numel() * t.element_size()
+    if nbytes == 0 or nbytes % multiple:
+        raise ProbeError(f"{what}: {nbytes} bytes is not a nonzero multiple of {multiple}")
+    if t.data_ptr() % align:
+        raise ProbeError(f"{what}: the tensor's storage is not {align}-byte aligned")
+    return nbytes
+
+
+def _stream_of(t, stream):
+    import torch
+
+    s = stream if stream is not None else torch.cuda.current_stream(t.device)
+    return C.c_void_p(s.cuda_stream)
+
+
+def count_diff(a, b, stream=None) -> int:
+    """Number of 16-byte words in which two device tensors of the same size differ: the
+    burn-in's compare kernel (gm_probe_count_diff). Waits for the result."""
+    import torch
+
+    na, nb = _dev_bytes(a, "count_diff"), _dev_bytes(b, "count_diff")
+    if na != nb or a.device != b.device:
+        raise ProbeError(f"count_diff: {na} and {nb} bytes, or different devices")
+    n = C.c_uint64(0)
+    with torch.cuda.device(a.device):
+        _check(_native.probe().gm_probe_count_diff(a.data_ptr(), b.data_ptr(), na,
+                                                   _stream_of(a, stream), C.byref(n)),
+               "count_diff")
+    return n.value
+
+
+def fill_bf16(t, seed: int, stream=None):
+    """Fill a bf16 (or int16/uint16) device tensor with the burn-in's operand sequence for
+    ``seed`` (gm_probe_fill_bf16; formula in native/include/gm_probe.h). Asynchronous."""
+    import torch
+
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.bfloat16, torch.int16,
+                                                          torch.uint16):
+        raise ProbeError("fill_bf16 expects a bf16, int16 or uint16 torch tensor")
+    if not isinstance(seed, int) or isinstance(seed, bool) or not 0 <= seed < 1 << 32:
+        raise ProbeError("fill_bf16: seed must be an integer in [0, 2^32)")
+    _dev_bytes(t, "fill_bf16", align=2, multiple=2)
+    with torch.cuda.device(t.device):
+        _check(_native.probe().gm_probe_fill_bf16(t.data_ptr(), t.numel(), seed,
+                                                  _stream_of(t, stream)), "fill_bf16")
+    return t
+
+
+def copy(variant: int, src, dst, blocks_per_cu: int = 8, stream=None):
+    """One launch of HBM copy variant ``variant`` (0..6, see gm_probe.h) from ``src`` to ``dst``,
+    device tensors of the same size in bytes (gm_probe_copy). Asynchronous."""
+    import torch
+
+    ns, nd = _dev_bytes(src, "copy"), _dev_bytes(dst, "copy")
+    if ns != nd or src.device != dst.device:
+        raise ProbeError(f"copy: {ns} and {nd} bytes, or different devices")
+    with torch.cuda.device(src.device):
+        _check(_native.probe().gm_probe_copy(variant, src.data_ptr(), dst.data_ptr(), ns,
+                                             blocks_per_cu, _stream_of(src, stream)), "copy")
+    return dst
+
+
+READ_SINK_WORDS = 1024
+READ_MAGIC = 0x9E3779B9       # a thread stores only if the XOR of the words it read is this
+
+
+def read(src, sink, blocks_per_cu: int = 2, stream=None):
+    """One launch of the HBM read stream over ``src`` (gm_probe_read). ``sink`` is a device
+    tensor of 1024 int32/uint32: a thread of block ``b`` writes ``sink[b & 1023] = READ_MAGIC``
+    only if the XOR of the 32-bit words it read (elements 256 apart in the block's chunk) equals
+    READ_MAGIC. Asynchronous."""
+    import torch
+
+    ns = _dev_bytes(src, "read")
+    if not isinstance(sink, torch.Tensor) or sink.dtype not in (torch.int32, torch.uint32) \
+            or sink.numel() != READ_SINK_WORDS or sink.device != src.device:
+        raise ProbeError(f"read: sink must be {READ_SINK_WORDS} int32 on the source's device")
+    _dev_bytes(sink, "read", align=4, multiple=4)
+    with torch.cuda.device(src.device):
+        _check(_native.probe().gm_probe_read(src.data_ptr(), sink.data_ptr(), ns, blocks_per_cu,
+                                             _stream_of(src, stream)), "read")
+    return sink
 
 
 def p2p(dev_a: int, dev_b: int, nbytes: int = 256 << 20, iters: int = 10) -> Dict:

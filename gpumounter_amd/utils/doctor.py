@@ -281,12 +281,13 @@ async def _check_priority(cfg, kube) -> List[Check]:
 
 
 def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
-               memtest_flip=None) -> List[Check]:
+               memtest_flip=None, burn_in_flip=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
     test over that many bytes per GPU (negative: 90 % of what is free on it); ``memtest_flip``
-    = (offset, mask) is its negative control. A GPU that fails here should not be handed out."""
+    = (offset, mask) is its negative control, ``burn_in_flip`` = [(element, mask), ...] the
+    burn-in's (see :func:`probe.burn_in`). A GPU that fails here should not be handed out."""
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import probe
 
@@ -314,7 +315,7 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                       f"(first launch {cold / 1e3:.0f} ms)")
             status = "ok" if arch == "gfx950" else "warn"
             if burn_in_s > 0:
-                b = probe.burn_in(d, burn_in_s)
+                b = probe.burn_in(d, burn_in_s, _flips=burn_in_flip)
                 detail += (f", burn-in {b['seconds']:g} s {b['tflops']:.0f} TF/s "
                            f"{b['mismatches']} mismatching words")
                 status = status if b["ok"] else "fail"

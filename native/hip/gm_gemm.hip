@@ -239,7 +239,9 @@ __global__ __launch_bounds__(512) void k_gemm_nt256p(const __bf16* __restrict__ 
         C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] = (__bf16)acc[i][j][r];
 }
 
-// Deterministic uniform [-1, 1) bf16 fill (random operands: zero-filled ones overstate a GEMM).
+// Deterministic uniform [-1, 1] bf16 fill (random operands: zero-filled ones overstate a GEMM).
+// The fp32 value lies in [-1, 1); the ones within half a bf16 step of 1 round up to exactly 1.0.
+// The element index is hashed as 32 bits, so the sequence repeats after 2^32 elements.
 __global__ __launch_bounds__(256) void k_fill_bf16(__bf16* dst, size_t n, uint32_t seed) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
        i += (size_t)gridDim.x * blockDim.x) {
@@ -265,6 +267,19 @@ __global__ __launch_bounds__(256) void k_count_diff(const u32x4* __restrict__ a,
   }
   for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, kWave);
   if ((threadIdx.x & 63) == 0 && local) atomicAdd(count, local);
+}
+
+// The one launch of each helper kernel: the drivers below and the caller-owned-buffer entry
+// points share them, so a test of the latter runs the grids the former use.
+int launch_fill_bf16(void* dst, size_t n, uint32_t seed, hipStream_t s) {
+  hipLaunchKernelGGL(k_fill_bf16, dim3(4096), dim3(256), 0, s, (__bf16*)dst, n, seed);
+  return (int)hipGetLastError();
+}
+
+int launch_count_diff(const void* a, const void* b, size_t vec, void* count, hipStream_t s) {
+  hipLaunchKernelGGL(k_count_diff, dim3(2048), dim3(256), 0, s, (const u32x4*)a, (const u32x4*)b,
+                     vec, (unsigned long long*)count);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -307,13 +322,12 @@ int gm_probe_gemm_nt_tflops(int dev, int M, int N, int K, int iters, double* tfl
   GM_CHECK(da.alloc((size_t)M * K * 2));
   GM_CHECK(db.alloc((size_t)N * K * 2));
   GM_CHECK(dc.alloc((size_t)M * N * 2));
-  hipLaunchKernelGGL(k_fill_bf16, dim3(4096), dim3(256), 0, 0, (__bf16*)da.p, (size_t)M * K,
-                     0x1234u);
-  hipLaunchKernelGGL(k_fill_bf16, dim3(4096), dim3(256), 0, 0, (__bf16*)db.p, (size_t)N * K,
-                     0x9876u);
+  int e = launch_fill_bf16(da.p, (size_t)M * K, 0x1234u, nullptr);
+  if (!e) e = launch_fill_bf16(db.p, (size_t)N * K, 0x9876u, nullptr);
+  if (e) return e;
   Events ev;
   GM_CHECK(ev.create());
-  int e = gm_probe_gemm_nt(da.p, db.p, dc.p, M, N, K, nullptr);  // warm-up
+  e = gm_probe_gemm_nt(da.p, db.p, dc.p, M, N, K, nullptr);  // warm-up
   if (!e) e = (int)hipEventRecord(ev.e0, nullptr);
   for (int i = 0; i < iters && !e; ++i) e = gm_probe_gemm_nt(da.p, db.p, dc.p, M, N, K, nullptr);
   if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
@@ -324,16 +338,52 @@ int gm_probe_gemm_nt_tflops(int dev, int M, int N, int K, int iters, double* tfl
   return e;
 }
 
+int gm_probe_count_diff(const void* a, const void* b, uint64_t bytes, void* stream,
+                        uint64_t* count) {
+  if (!count) return (int)hipErrorInvalidValue;
+  *count = 0;
+  if (!a || !b || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || bytes == 0 || (bytes & 15))
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf dcount;
+  GM_CHECK(dcount.alloc(sizeof(unsigned long long)));
+  GM_CHECK(hipMemsetAsync(dcount.p, 0, sizeof(unsigned long long), s));
+  if (int e = launch_count_diff(a, b, bytes / 16, dcount.p, s)) return e;
+  unsigned long long h = 0;
+  GM_CHECK(hipMemcpyAsync(&h, dcount.p, sizeof(h), hipMemcpyDeviceToHost, s));
+  GM_CHECK(hipStreamSynchronize(s));
+  *count = h;
+  return 0;
+}
+
+int gm_probe_fill_bf16(void* dst, uint64_t n_elems, uint32_t seed, void* stream) {
+  if (!dst || ((uintptr_t)dst & 1) || n_elems == 0) return (int)hipErrorInvalidValue;
+  return launch_fill_bf16(dst, n_elems, seed, (hipStream_t)stream);
+}
+
 int gm_probe_burn_in(int dev, int n, double seconds, double* tflops, uint64_t* mismatches,
                      int* iters) {
+  return gm_probe_burn_in_flip(dev, n, seconds, 0, nullptr, nullptr, tflops, mismatches, iters);
+}
+
+int gm_probe_burn_in_flip(int dev, int n, double seconds, int n_flips,
+                          const uint64_t* flip_elems, const uint16_t* flip_masks,
+                          double* tflops, uint64_t* mismatches, int* iters) {
   using namespace g256;
   *tflops = 0;
   *mismatches = 0;
   *iters = 0;
   if (n <= 0 || n % TM || seconds <= 0) return (int)hipErrorInvalidValue;
+  const size_t elems = (size_t)n * n;
+  if (n_flips < 0 || (n_flips > 0 && (!flip_elems || !flip_masks)))
+    return (int)hipErrorInvalidValue;
+  for (int i = 0; i < n_flips; ++i) {
+    if (flip_elems[i] >= elems || flip_masks[i] == 0) return (int)hipErrorInvalidValue;
+    for (int j = 0; j < i; ++j)  // a repeated element could cancel its own flip
+      if (flip_elems[j] == flip_elems[i]) return (int)hipErrorInvalidValue;
+  }
   DeviceGuard g(dev);
   if (!g.ok) return (int)hipErrorInvalidDevice;
-  const size_t elems = (size_t)n * n;
   DevBuf da, db, dref, dc, dcount;
   GM_CHECK(da.alloc(elems * 2));
   GM_CHECK(db.alloc(elems * 2));
@@ -341,10 +391,19 @@ int gm_probe_burn_in(int dev, int n, double seconds, double* tflops, uint64_t* m
   GM_CHECK(dc.alloc(elems * 2));
   GM_CHECK(dcount.alloc(sizeof(unsigned long long)));
   GM_CHECK(hipMemset(dcount.p, 0, sizeof(unsigned long long)));
-  hipLaunchKernelGGL(k_fill_bf16, dim3(4096), dim3(256), 0, 0, (__bf16*)da.p, elems, 0x5151u);
-  hipLaunchKernelGGL(k_fill_bf16, dim3(4096), dim3(256), 0, 0, (__bf16*)db.p, elems, 0xa3a3u);
-  int e = gm_probe_gemm_nt(da.p, db.p, dref.p, n, n, n, nullptr);  // the reference result
+  int e = launch_fill_bf16(da.p, elems, 0x5151u, nullptr);
+  if (!e) e = launch_fill_bf16(db.p, elems, 0xa3a3u, nullptr);
+  if (!e) e = gm_probe_gemm_nt(da.p, db.p, dref.p, n, n, n, nullptr);  // the reference result
   if (e) return e;
+  // Negative control: corrupt the finished reference, through the host like the memtest's flip.
+  // The blocking copies on the null stream wait for the GEMM; the loop below is untouched.
+  for (int i = 0; i < n_flips; ++i) {
+    uint16_t* at = (uint16_t*)dref.p + flip_elems[i];
+    uint16_t v = 0;
+    GM_CHECK(hipMemcpy(&v, at, sizeof(v), hipMemcpyDeviceToHost));
+    v ^= flip_masks[i];
+    GM_CHECK(hipMemcpy(at, &v, sizeof(v), hipMemcpyHostToDevice));
+  }
   Events ev;
   GM_CHECK(ev.create());
   GM_CHECK(hipEventRecord(ev.e0, nullptr));
@@ -356,12 +415,7 @@ int gm_probe_burn_in(int dev, int n, double seconds, double* tflops, uint64_t* m
   while (!e) {
     for (int i = 0; i < 8 && !e; ++i) {
       e = gm_probe_gemm_nt(da.p, db.p, dc.p, n, n, n, nullptr);
-      if (!e) {
-        hipLaunchKernelGGL(k_count_diff, dim3(2048), dim3(256), 0, 0,
-                           (const u32x4*)dc.p, (const u32x4*)dref.p, vec,
-                           (unsigned long long*)dcount.p);
-        e = (int)hipGetLastError();
-      }
+      if (!e) e = launch_count_diff(dc.p, dref.p, vec, dcount.p, nullptr);
       ++done;
     }
     if (!e) e = (int)hipDeviceSynchronize();

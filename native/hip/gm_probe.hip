@@ -293,6 +293,57 @@ Scratch* scratch(int dev) {
   return &s;
 }
 
+// ------------------------------------------------------------------ HBM stream launches
+// One launch of a copy variant over n 16-byte elements: the timed driver and gm_probe_copy both
+// come through here, so a test of the latter checks the geometry the former times.
+bool copy_variant_ok(int variant) { return variant >= 0 && variant <= 6; }
+
+int launch_copy(int variant, const float4* src, float4* dst, size_t n, int blocks,
+                hipStream_t s) {
+  if (blocks <= 0) return (int)hipErrorInvalidValue;
+  const size_t per_block = ((n + blocks - 1) / blocks + 1023) / 1024 * 1024;
+  const dim3 grid(blocks), block(256);
+  switch (variant) {
+    case 0: hipLaunchKernelGGL(k_copy, grid, block, 0, s, src, dst, n); break;
+    case 1:
+      hipLaunchKernelGGL((k_copy_chunk<4, false>), grid, block, 0, s, src, dst, n, per_block);
+      break;
+    case 2:
+      hipLaunchKernelGGL((k_copy_chunk<4, true>), grid, block, 0, s, src, dst, n, per_block);
+      break;
+    case 3:
+      hipLaunchKernelGGL((k_copy_chunk<8, true>), grid, block, 0, s, src, dst, n, per_block);
+      break;
+    case 4:
+      hipLaunchKernelGGL((k_copy_chunk<8, false>), grid, block, 0, s, src, dst, n, per_block);
+      break;
+    case 5: hipLaunchKernelGGL((k_copy_pipe<4>), grid, block, 0, s, src, dst, n, per_block); break;
+    case 6: hipLaunchKernelGGL((k_copy_pipe<2>), grid, block, 0, s, src, dst, n, per_block); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
+}
+
+// One launch of the read stream; `sink` holds kReadSinkWords uint32 (block b may write word
+// b & 1023).
+constexpr size_t kReadSinkWords = 1024;
+
+int launch_read(const float4* src, uint32_t* sink, size_t n, int blocks, hipStream_t s) {
+  if (blocks <= 0) return (int)hipErrorInvalidValue;
+  const size_t per_block = ((n + blocks - 1) / blocks + 2047) / 2048 * 2048;
+  hipLaunchKernelGGL((k_read_chunk<8>), dim3(blocks), dim3(256), 0, s, src, sink, n, per_block);
+  return (int)hipGetLastError();
+}
+
+bool aligned16(const void* p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
+
+int current_cus(int* cus) {
+  int dev = 0;
+  GM_CHECK(hipGetDevice(&dev));
+  GM_CHECK(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+  return 0;
+}
+
 uint16_t f2bf(float f) {
   uint32_t u;
   memcpy(&u, &f, 4);
@@ -368,111 +419,92 @@ int gm_probe_quick(int dev, int* ok, double* elapsed_us) {
   return 0;
 }
 
+int gm_probe_copy(int variant, const void* src, void* dst, uint64_t bytes, int blocks_per_cu,
+                  void* stream) {
+  if (!aligned16(src) || !aligned16(dst) || bytes == 0 || (bytes & 15) || blocks_per_cu <= 0 ||
+      !copy_variant_ok(variant))
+    return (int)hipErrorInvalidValue;
+  const uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
+  if (s < d + bytes && d < s + bytes) return (int)hipErrorInvalidValue;  // __restrict__ kernels
+  int cus = 0;
+  if (int e = current_cus(&cus)) return e;
+  return launch_copy(variant, (const float4*)src, (float4*)dst, bytes / sizeof(float4),
+                     cus * blocks_per_cu, (hipStream_t)stream);
+}
+
+int gm_probe_read(const void* src, uint32_t* sink, uint64_t bytes, int blocks_per_cu,
+                  void* stream) {
+  if (!aligned16(src) || sink == nullptr || ((uintptr_t)sink & 3) || bytes == 0 || (bytes & 15) ||
+      blocks_per_cu <= 0)
+    return (int)hipErrorInvalidValue;
+  int cus = 0;
+  if (int e = current_cus(&cus)) return e;
+  return launch_read((const float4*)src, sink, bytes / sizeof(float4), cus * blocks_per_cu,
+                     (hipStream_t)stream);
+}
+
 int gm_probe_hbm_copy_variant(int dev, int variant, uint64_t bytes, int iters,
                               int blocks_per_cu, double* gbps) {
   *gbps = 0;
+  bytes &= ~(uint64_t)15;
+  if (bytes == 0 || iters <= 0 || blocks_per_cu <= 0 || !copy_variant_ok(variant))
+    return (int)hipErrorInvalidValue;
   DeviceGuard g(dev);
   if (!g.ok) return (int)hipErrorInvalidDevice;
-  bytes &= ~(uint64_t)15;
-  if (bytes == 0 || iters <= 0 || blocks_per_cu <= 0) return (int)hipErrorInvalidValue;
   hipDeviceProp_t p;
   GM_CHECK(hipGetDeviceProperties(&p, dev));
-  float4 *src = nullptr, *dst = nullptr;
-  GM_CHECK(hipMalloc(&src, bytes));
-  hipError_t e = hipMalloc(&dst, bytes);
-  if (e != hipSuccess) {
-    (void)hipFree(src);
-    return (int)e;
-  }
+  DevBuf src, dst;
+  GM_CHECK(src.alloc(bytes));
+  GM_CHECK(dst.alloc(bytes));
   const size_t n = bytes / sizeof(float4);
   const int blocks = p.multiProcessorCount * blocks_per_cu;
-  const size_t per_block = ((n + blocks - 1) / blocks + 1023) / 1024 * 1024;
   auto launch = [&]() {
-    switch (variant) {
-      case 0: hipLaunchKernelGGL(k_copy, dim3(blocks), dim3(256), 0, 0, src, dst, n); break;
-      case 1:
-        hipLaunchKernelGGL((k_copy_chunk<4, false>), dim3(blocks), dim3(256), 0, 0, src, dst,
-                           n, per_block);
-        break;
-      case 3:
-        hipLaunchKernelGGL((k_copy_chunk<8, true>), dim3(blocks), dim3(256), 0, 0, src, dst,
-                           n, per_block);
-        break;
-      case 4:
-        hipLaunchKernelGGL((k_copy_chunk<8, false>), dim3(blocks), dim3(256), 0, 0, src, dst,
-                           n, per_block);
-        break;
-      case 5:
-        hipLaunchKernelGGL((k_copy_pipe<4>), dim3(blocks), dim3(256), 0, 0, src, dst, n,
-                           per_block);
-        break;
-      case 6:
-        hipLaunchKernelGGL((k_copy_pipe<2>), dim3(blocks), dim3(256), 0, 0, src, dst, n,
-                           per_block);
-        break;
-      default:
-        hipLaunchKernelGGL((k_copy_chunk<4, true>), dim3(blocks), dim3(256), 0, 0, src, dst,
-                           n, per_block);
-    }
+    return launch_copy(variant, (const float4*)src.p, (float4*)dst.p, n, blocks, nullptr);
   };
-  hipEvent_t a, b;
-  (void)hipEventCreate(&a);
-  (void)hipEventCreate(&b);
-  hipLaunchKernelGGL(k_fill, dim3(blocks), dim3(256), 0, 0, src, n, 1.0f);
-  launch();
-  (void)hipEventRecord(a, 0);
-  for (int i = 0; i < iters; ++i) launch();
-  (void)hipEventRecord(b, 0);
-  e = hipEventSynchronize(b);
+  Events ev;
+  GM_CHECK(ev.create());
+  hipLaunchKernelGGL(k_fill, dim3(blocks), dim3(256), 0, 0, (float4*)src.p, n, 1.0f);
+  int e = (int)hipGetLastError();
+  if (!e) e = launch();
+  if (!e) e = (int)hipEventRecord(ev.e0, nullptr);
+  for (int i = 0; i < iters && !e; ++i) e = launch();
+  if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
+  if (!e) e = (int)hipEventSynchronize(ev.e1);
   float ms = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-  if (e == hipSuccess && ms > 0) *gbps = 2.0 * (double)bytes * iters / (ms * 1e-3) / 1e9;
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  (void)hipFree(src);
-  (void)hipFree(dst);
-  return (int)e;
+  if (!e) e = (int)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+  if (!e && ms > 0) *gbps = 2.0 * (double)bytes * iters / (ms * 1e-3) / 1e9;
+  return e;
 }
 
 int gm_probe_hbm_read(int dev, uint64_t bytes, int iters, int blocks_per_cu, double* gbps) {
   *gbps = 0;
-  DeviceGuard g(dev);
-  if (!g.ok) return (int)hipErrorInvalidDevice;
   bytes &= ~(uint64_t)15;
   if (bytes == 0 || iters <= 0 || blocks_per_cu <= 0) return (int)hipErrorInvalidValue;
+  DeviceGuard g(dev);
+  if (!g.ok) return (int)hipErrorInvalidDevice;
   hipDeviceProp_t p;
   GM_CHECK(hipGetDeviceProperties(&p, dev));
-  float4* src = nullptr;
-  uint32_t* sink = nullptr;
-  GM_CHECK(hipMalloc(&src, bytes));
-  hipError_t e = hipMalloc(&sink, 1024 * sizeof(uint32_t));
-  if (e != hipSuccess) {
-    (void)hipFree(src);
-    return (int)e;
-  }
+  DevBuf src, sink;
+  GM_CHECK(src.alloc(bytes));
+  GM_CHECK(sink.alloc(kReadSinkWords * sizeof(uint32_t)));
   const size_t n = bytes / sizeof(float4);
   const int blocks = p.multiProcessorCount * blocks_per_cu;
-  const size_t per_block = ((n + blocks - 1) / blocks + 2047) / 2048 * 2048;
   auto launch = [&]() {
-    hipLaunchKernelGGL((k_read_chunk<8>), dim3(blocks), dim3(256), 0, 0, src, sink, n, per_block);
+    return launch_read((const float4*)src.p, (uint32_t*)sink.p, n, blocks, nullptr);
   };
-  hipEvent_t a, b;
-  (void)hipEventCreate(&a);
-  (void)hipEventCreate(&b);
-  hipLaunchKernelGGL(k_fill, dim3(blocks), dim3(256), 0, 0, src, n, 1.0f);
-  launch();
-  (void)hipEventRecord(a, 0);
-  for (int i = 0; i < iters; ++i) launch();
-  (void)hipEventRecord(b, 0);
-  e = hipEventSynchronize(b);
+  Events ev;
+  GM_CHECK(ev.create());
+  hipLaunchKernelGGL(k_fill, dim3(blocks), dim3(256), 0, 0, (float4*)src.p, n, 1.0f);
+  int e = (int)hipGetLastError();
+  if (!e) e = launch();
+  if (!e) e = (int)hipEventRecord(ev.e0, nullptr);
+  for (int i = 0; i < iters && !e; ++i) e = launch();
+  if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
+  if (!e) e = (int)hipEventSynchronize(ev.e1);
   float ms = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-  if (e == hipSuccess && ms > 0) *gbps = (double)bytes * iters / (ms * 1e-3) / 1e9;
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  (void)hipFree(src);
-  (void)hipFree(sink);
-  return (int)e;
+  if (!e) e = (int)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+  if (!e && ms > 0) *gbps = (double)bytes * iters / (ms * 1e-3) / 1e9;
+  return e;
 }
 
 int gm_probe_mfma_peak_variant(int dev, int variant, int iters, int blocks_per_cu,

@@ -31,15 +31,31 @@ int gm_probe_find_device(const char* bdf, int* dev);
 // Liveness: launches one wave64 kernel that writes lane ids and a checksum; verifies on host.
 // *elapsed_us = launch→readback wall time.
 int gm_probe_quick(int dev, int* ok, double* elapsed_us);
-// HBM3E stream: float4 copy of `bytes` for `iters`; *gbps = (read+write) bytes / time.
+// HBM3E stream: float4 copy of `bytes` for `iters`; *gbps = (read+write) bytes / time. The
+// default variant is 2. Both timed drivers round `bytes` down to a multiple of 16 and return the
+// HIP error of a failed launch instead of a rate.
 int gm_probe_hbm_copy(int dev, uint64_t bytes, int iters, double* gbps);
 // Read-only HBM stream over `bytes` (8 nontemporal 16-B loads in flight per lane); GB/s read.
 int gm_probe_hbm_read(int dev, uint64_t bytes, int iters, int blocks_per_cu, double* gbps);
 // Tuning variants: 0 grid-stride, 1 chunked 4×16B/lane, 2 chunked 4 + nontemporal,
 // 3 chunked 8 + nontemporal, 4 chunked 8, 5/6 software-pipelined 4/2 (next loads before
-// current stores), nontemporal.
+// current stores), nontemporal. Any other variant is hipErrorInvalidValue.
 int gm_probe_hbm_copy_variant(int dev, int variant, uint64_t bytes, int iters,
                               int blocks_per_cu, double* gbps);
+// The launches the two timed drivers repeat, on caller-owned device buffers of the current
+// device (`stream` may be NULL; asynchronous; the launch error is returned). Geometry: CUs ×
+// blocks_per_cu blocks of 256 threads, each block a contiguous chunk of 16-byte elements rounded
+// up to 1024 (copy) or 2048 (read) elements. Pointers 16-byte aligned, `bytes` a nonzero multiple
+// of 16 (not rounded here), blocks_per_cu > 0, variant 0..6, src and dst disjoint: anything else
+// is hipErrorInvalidValue before any HIP call.
+// Exactly one launch of copy variant `variant`: dst[0, bytes) = src[0, bytes).
+int gm_probe_copy(int variant, const void* src, void* dst, uint64_t bytes, int blocks_per_cu,
+                  void* stream);
+// Exactly one launch of the read stream. `sink` is 1024 uint32: every thread XORs the 32-bit
+// words it reads (elements 256 apart in its block's chunk) and, only if that fold equals
+// 0x9e3779b9, writes it to sink[b & 1023], b its block.
+int gm_probe_read(const void* src, uint32_t* sink, uint64_t bytes, int blocks_per_cu,
+                  void* stream);
 // variant 0: v_mfma_f32_32x32x16_bf16 × 4 chains, 1: v_mfma_f32_16x16x32_bf16 × 4 chains,
 // 2: 16x16x32 × 8 chains.
 int gm_probe_mfma_peak_variant(int dev, int variant, int iters, int blocks_per_cu,
@@ -55,14 +71,35 @@ int gm_probe_gemm_nt(const void* A, const void* Bt, void* C, int M, int N, int K
 // Schedule variants of the same kernel (A/B measurements; bench/gemm_sweep.py).
 int gm_probe_gemm_nt_variant(int variant, const void* A, const void* Bt, void* C, int M, int N,
                              int K, void* stream);
-// Dense bf16 TF/s of gm_probe_gemm_nt on uniform [-1,1) operands, `iters` back-to-back launches.
+// Dense bf16 TF/s of gm_probe_gemm_nt on uniform [-1,1] operands (gm_probe_fill_bf16), `iters`
+// back-to-back launches.
 int gm_probe_gemm_nt_tflops(int dev, int M, int N, int K, int iters, double* tflops);
-// Burn-in: back-to-back n³ GEMMs (gm_probe_gemm_nt) for `seconds` on uniform [-1,1) operands;
+// The operand fill of the two drivers below, on a caller-owned buffer of the current device:
+// dst[i] = bf16(float(h >> 8) · 2/2^24 − 1), rounded to nearest even, with
+//   h = (u32)i · 2654435761 ^ seed;  h ^= h >> 15;  h *= 2246822519;  h ^= h >> 13   (all u32).
+// The values lie in [-1, 1]: the fp32 value is below 1, but the largest ones round to exactly
+// 1.0 in bf16. The index is hashed as 32 bits, so the sequence repeats after 2^32 elements.
+// `dst` 2-byte aligned, n_elems > 0 (checked); asynchronous on `stream` (may be NULL).
+int gm_probe_fill_bf16(void* dst, uint64_t n_elems, uint32_t seed, void* stream);
+// Number of 16-byte words that differ between a and b (the burn-in's compare kernel, with the
+// burn-in's grid). Device pointers on the current device, both 16-byte aligned, `bytes` a nonzero
+// multiple of 16 (checked before any HIP call); `stream` may be NULL; waits for the result.
+int gm_probe_count_diff(const void* a, const void* b, uint64_t bytes, void* stream,
+                        uint64_t* count);
+// Burn-in: back-to-back n³ GEMMs (gm_probe_gemm_nt) for `seconds` on uniform [-1,1] operands;
 // every result is compared bit-for-bit with the first (the kernel is deterministic), so
 // *mismatches > 0 (16-B words that differ, summed over iterations) means silent data
 // corruption. *tflops includes the compare kernels. n % 256 == 0.
 int gm_probe_burn_in(int dev, int n, double seconds, double* tflops, uint64_t* mismatches,
                      int* iters);
+// The burn-in's negative control (gm_probe_burn_in is its n_flips == 0 case): after the reference
+// result is computed and before the loop starts, bf16 element flip_elems[i] (< n², all distinct)
+// of the reference is XORed with the nonzero flip_masks[i] through a host round trip. The loop
+// itself is unchanged, so *mismatches == *iters × (distinct 16-byte words among the flipped
+// elements, i.e. distinct flip_elems[i] / 8). Bad flips: hipErrorInvalidValue before any HIP call.
+int gm_probe_burn_in_flip(int dev, int n, double seconds, int n_flips,
+                          const uint64_t* flip_elems, const uint16_t* flip_masks,
+                          double* tflops, uint64_t* mismatches, int* iters);
 // Self-contained numerics check of gm_probe_gemm_bf16 against a host fp32 reference.
 int gm_probe_gemm_check(int dev, int M, int N, int K, double* max_abs_err, double* ref_scale);
 // xGMI / PCIe peer copy a→b; *can_access from hipDeviceCanAccessPeer.
