@@ -234,6 +234,39 @@ class MemtestResult(C.Structure):
                 ("read_gbps", C.c_double), ("rw_gbps", C.c_double)]
 
 
+CUSCAN_MAX_RECORDS = 16       # native/include/gm_probe.h GM_CUSCAN_MAX_RECORDS
+CUSCAN_IDS = 4096             # GM_CUSCAN_IDS
+CUSCAN_ANY = 0xFFFFFFFF       # GM_CUSCAN_ANY
+
+
+class CuscanRecord(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("simd", C.c_uint32), ("test", C.c_uint32),
+                ("thread", C.c_uint32), ("word", C.c_uint32), ("expected", C.c_uint32),
+                ("got", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class CuscanInject(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("test", C.c_uint32), ("thread", C.c_uint32),
+                ("word", C.c_uint32), ("mask", C.c_uint32)]
+
+
+class CuscanCu(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("xcc", C.c_uint32), ("se", C.c_uint32), ("sh", C.c_uint32),
+                ("cu", C.c_uint32), ("runs", C.c_uint32), ("failed_runs", C.c_uint32),
+                ("tests_failed", C.c_uint32), ("simds_seen", C.c_uint32),
+                ("simds_failed", C.c_uint32)]
+
+
+class CuscanResult(C.Structure):
+    _fields_ = [("cus_expected", C.c_uint32), ("cus_seen", C.c_uint32), ("complete", C.c_uint32),
+                ("rounds", C.c_uint32), ("blocks_run", C.c_uint64),
+                ("words_in_error", C.c_uint64), ("blocks_four_simds", C.c_uint64),
+                ("failed_cus", C.c_uint32), ("records_filled", C.c_uint32),
+                ("xcc_cus", C.c_uint32 * 16),
+                ("records", CuscanRecord * CUSCAN_MAX_RECORDS),
+                ("seconds", C.c_double), ("kernel_ms", C.c_double)]
+
+
 def _prefer_torch_hip_runtime() -> None:
     """A process can hold only one HIP runtime, and ``libamdhip64.so.7`` is resolved by soname:
     whichever copy is loaded first (ROCm's /opt/rocm/lib or the one PyTorch bundles) serves
@@ -305,6 +338,14 @@ def probe() -> C.CDLL:
                                          C.c_uint64, C.c_uint64, C.c_uint64,
                                          C.POINTER(MemtestResult)]
         lib.gm_probe_memtest_store_variant.argtypes = [C.c_int]
+        lib.gm_probe_cuscan_expected.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32,
+                                                 C.POINTER(C.c_uint32)]
+        lib.gm_probe_cuscan_signature.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
+        lib.gm_probe_cuscan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int,
+                                        C.c_int, C.POINTER(CuscanInject),
+                                        C.POINTER(CuscanResult), C.POINTER(CuscanCu), C.c_int,
+                                        C.POINTER(C.c_int)]
         lib.gm_probe_strerror.argtypes = [C.c_int]
         lib.gm_probe_strerror.restype = C.c_char_p
         lib._gm_typed = True

@@ -9,12 +9,15 @@
                                        [--memtest [SIZE]] [--memtest-passes N]
                                        [--memtest-patterns addr,solid,checker,walk,random]
                                        [--memtest-flip OFFSET:MASK]          # HBM pattern test
+                                       [--cu-scan] [--cu-scan-tests int,f32,mfma,lds]
+                                       [--cu-scan-rounds N]                  # per-CU self-test
+                                       [--cu-scan-inject ID|any:TEST:THREAD:WORD:MASK]
     python -m gpumounter_amd add    --master URL --ns NS --pod P -n 2 [--entire] [--lease 3600]
     python -m gpumounter_amd remove --master URL --ns NS --pod P --uuid U [--uuid U2] [--force]
     python -m gpumounter_amd status --master URL --node NODE
     python -m gpumounter_amd bpf-dump --allow 226:128 --allow 511:0   # generated device program
     python -m gpumounter_amd doctor  [--json] [--skip-cluster] [--gpu [--burn-in 30]]  # preflight
-                                     [--gpu --memtest [SIZE]]
+                                     [--gpu --memtest [SIZE]] [--gpu --cu-scan]
     python -m gpumounter_amd config-doc > docs/CONFIG.md   # every GM_* setting, from the source
 
 The reference ships only the two daemons and documents curl calls (QuickStart.md:41-92); the
@@ -177,6 +180,19 @@ def _burn_in_flip(text):
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _cuscan_arg(kind):
+    """argparse type for the --cu-scan-* options: the parser in ops.cuscan, its refusal a usage
+    error."""
+    def conv(text):
+        from gpumounter_amd.ops import cuscan
+        try:
+            return getattr(cuscan, kind)(text)
+        except cuscan.ProbeError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    conv.__name__ = kind
+    return conv
+
+
 def _add_memtest_size(p, what: str) -> None:
     p.add_argument("--memtest", nargs="?", const=MEMTEST_AUTO, default=None, metavar="SIZE",
                    type=_memtest_arg("parse_size"), help=what)
@@ -188,6 +204,16 @@ def cmd_probe(args) -> int:
     if args.burn_in_flip and not args.burn_in:
         print("probe: --burn-in-flip needs --burn-in SECONDS", file=sys.stderr)
         return 2                      # a usage error, not a failed burn-in (exit 1)
+    if args.cu_scan_inject and not args.cu_scan:
+        print("probe: --cu-scan-inject needs --cu-scan", file=sys.stderr)
+        return 2
+    if not 1 <= args.cu_scan_rounds <= 1024:
+        print("probe: --cu-scan-rounds must be between 1 and 1024", file=sys.stderr)
+        return 2
+    if args.cu_scan_inject and args.cu_scan_inject[1] not in args.cu_scan_tests:
+        print(f"probe: --cu-scan-inject into {args.cu_scan_inject[1]!r}, which --cu-scan-tests "
+              f"leaves out", file=sys.stderr)
+        return 2
     if args.bdf:
         bdfs = args.bdf
     else:
@@ -206,6 +232,15 @@ def cmd_probe(args) -> int:
                 r["device"], _memtest_bytes(args.memtest), patterns=args.memtest_patterns,
                 passes=args.memtest_passes, _flip=args.memtest_flip)
             bad |= not r["memtest"]["ok"]
+    if args.cu_scan:
+        from gpumounter_amd.ops import cuscan
+
+        for r in res:
+            r["cuscan"] = cuscan.scan(r["device"], tests=args.cu_scan_tests,
+                                      min_rounds=args.cu_scan_rounds,
+                                      max_rounds=max(16, args.cu_scan_rounds),
+                                      _inject=args.cu_scan_inject)
+            bad |= not r["cuscan"]["ok"]
     print(json.dumps(res, indent=2))
     return 1 if bad else 0
 
@@ -361,8 +396,9 @@ def cmd_doctor(args) -> int:
     cfg = _cfg(args)
     memtest_bytes = args.memtest if args.memtest is not None else 0   # negative: automatic size
     checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
-                        gpu=args.gpu or bool(args.burn_in) or bool(memtest_bytes),
-                        burn_in_s=args.burn_in, memtest_bytes=memtest_bytes)
+                        gpu=args.gpu or bool(args.burn_in) or bool(memtest_bytes) or args.cu_scan,
+                        burn_in_s=args.burn_in, memtest_bytes=memtest_bytes,
+                        cu_scan=args.cu_scan)
     print(doctor.render(checks, args.json))
     return 1 if any(c.status == "fail" for c in checks) else 0
 
@@ -411,6 +447,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--memtest-flip", type=_memtest_arg("parse_flip"), default=None,
                    metavar="OFFSET:MASK",
                    help="negative control: corrupt that word after every fill; the test must fail")
+    p.add_argument("--cu-scan", action="store_true",
+                   help="per-CU self-test of every probed GPU: integer, fp32, MFMA and LDS "
+                        "known-answer tests on every compute unit (exit 1 on any wrong word)")
+    p.add_argument("--cu-scan-tests", type=_cuscan_arg("parse_tests"),
+                   default=("int", "f32", "mfma", "lds"), metavar="a,b,...")
+    p.add_argument("--cu-scan-rounds", type=int, default=1, metavar="N",
+                   help="at least N rounds (a round is one block per CU)")
+    p.add_argument("--cu-scan-inject", type=_cuscan_arg("parse_inject"), default=None,
+                   metavar="ID|any:TEST:THREAD:WORD:MASK",
+                   help="negative control: flip that signature word on that CU; the scan must "
+                        "name it")
     p.set_defaults(fn=cmd_probe)
     for name, fn in (("add", cmd_add), ("remove", cmd_remove), ("status", cmd_status)):
         p = sub.add_parser(name)
@@ -448,6 +495,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --gpu: sustained bit-checked GEMM load per GPU")
     _add_memtest_size(p, "with --gpu: HBM pattern test over SIZE bytes per GPU (default: 90 %% of "
                          "its free memory)")
+    p.add_argument("--cu-scan", action="store_true",
+                   help="with --gpu: per-CU self-test of every GPU; a failing CU is named")
     p.set_defaults(fn=cmd_doctor)
     p = sub.add_parser("bpf-dump")
     p.add_argument("--allow", action="append", default=[])

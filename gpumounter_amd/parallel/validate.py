@@ -13,7 +13,10 @@ starting a job on them — the reference offers nothing here:
    silent data corruption and throttling that a short probe misses;
 5. optionally (``--memtest [SIZE]``) the HBM pattern test on all GPUs at once
    (:func:`gpumounter_amd.ops.memtest.memtest`): SIZE bytes per GPU, by default 90 % of what is
-   free on it, written and read back in both polarities of five patterns.
+   free on it, written and read back in both polarities of five patterns;
+6. optionally (``--cu-scan``) the per-CU self-test on all GPUs at once
+   (:func:`gpumounter_amd.ops.cuscan.scan`): known-answer integer, fp32, MFMA and LDS tests on
+   every compute unit, a wrong word attributed to the CU that produced it.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -77,6 +80,8 @@ def main(argv=None) -> int:
     ap.add_argument("--memtest", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the HBM pattern test on every GPU at once over SIZE bytes each "
                          "(64M, 8G; default: 90 %% of the free memory)")
+    ap.add_argument("--cu-scan", action="store_true",
+                    help="then the per-CU self-test on every GPU at once")
     args = ap.parse_args(argv)
     memtest_bytes = None
     if args.memtest not in (None, "auto"):
@@ -130,6 +135,17 @@ def main(argv=None) -> int:
             mt = list(ex.map(lambda d: memtest.memtest(d, memtest_bytes), range(world)))
         report["memtest"] = mt
         report["ok"] &= all(m["ok"] for m in mt)
+    if args.cu_scan and not args.cpu_ranks:
+        from concurrent.futures import ThreadPoolExecutor
+
+        from gpumounter_amd.ops import cuscan
+
+        with ThreadPoolExecutor(max_workers=world) as ex:
+            cs = list(ex.map(cuscan.scan, range(world)))
+        for c in cs:
+            del c["per_cu"]               # one line per CU and GPU; "failed" names the bad ones
+        report["cuscan"] = cs
+        report["ok"] &= all(c["ok"] for c in cs)
     print(json.dumps(report))
     return 0 if report["ok"] else 1
 

@@ -281,13 +281,17 @@ async def _check_priority(cfg, kube) -> List[Check]:
 
 
 def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
-               memtest_flip=None, burn_in_flip=None) -> List[Check]:
+               memtest_flip=None, burn_in_flip=None, cu_scan: bool = False,
+               cu_scan_inject=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
     test over that many bytes per GPU (negative: 90 % of what is free on it); ``memtest_flip``
     = (offset, mask) is its negative control, ``burn_in_flip`` = [(element, mask), ...] the
-    burn-in's (see :func:`probe.burn_in`). A GPU that fails here should not be handed out."""
+    burn-in's (see :func:`probe.burn_in`). With ``cu_scan`` also the per-CU self-test
+    (:func:`gpumounter_amd.ops.cuscan.scan`): a CU with a wrong word fails the check and is named;
+    a scan that did not reach every CU is stated and does not fail it; ``cu_scan_inject`` is its
+    negative control. A GPU that fails here should not be handed out."""
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import probe
 
@@ -327,6 +331,17 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                 detail += (f", memtest {m['bytes'] / 2**30:.2f} GiB {m['read_gbps']:.0f} / "
                            f"{m['write_gbps']:.0f} GB/s {m['errors']} bad words")
                 status = status if m["ok"] else "fail"
+            if cu_scan:
+                from gpumounter_amd.ops import cuscan
+
+                c = cuscan.scan(d, _inject=cu_scan_inject)
+                detail += (f", cu-scan {c['cus_seen']}/{c['cus_expected']} CUs in {c['rounds']} "
+                           f"round(s) {c['kernel_ms']:.2f} ms {c['words_in_error']} wrong words")
+                if not c["complete"]:
+                    detail += " (incomplete: not every CU was reached)"
+                if not c["ok"]:
+                    detail += f", failed: {cuscan.describe_failed(c)}"
+                    status = "fail"
             out.append(Check(f"gpu{d}", status, detail))
         except Exception as e:  # noqa: BLE001 - a faulting GPU is exactly what this finds
             out.append(Check(f"gpu{d}", "fail", f"probe failed: {e}"))
@@ -337,11 +352,12 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
 
 
 def run(cfg, skip_cluster: bool = False, gpu: bool = False,
-        burn_in_s: float = 0.0, *, memtest_bytes: int = 0) -> List[Check]:
+        burn_in_s: float = 0.0, *, memtest_bytes: int = 0, cu_scan: bool = False) -> List[Check]:
     checks = check_inventory(cfg) + check_cgroup(cfg) + check_devnodes(cfg) + \
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
-        checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes)
+        extra = {"cu_scan": True} if cu_scan else {}
+        checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes, **extra)
     if not skip_cluster:
         async def both():
             return await _check_kubelet(cfg) + await _check_apiserver(cfg)

@@ -1,5 +1,5 @@
 // gm_probe_common.h — shared by the gfx950 probe translation units (gm_probe.hip, gm_gemm.hip,
-// gm_memtest.hip):
+// gm_memtest.hip, gm_cuscan.hip):
 // vector types, device selection guard, error macro, owning device buffer / event pair.
 // Everything is in an anonymous namespace: each translation unit gets its own copy.
 #pragma once

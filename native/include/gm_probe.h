@@ -183,6 +183,132 @@ int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pat
 // Returns the previous setting; any other value only queries.
 int gm_probe_memtest_store_variant(int nontemporal);
 
+// ------------------------------------------------------------------ per-CU self-test (CU scan)
+// One kernel runs the selected tests in a 256-thread block (4 waves) that statically declares the
+// whole 160 KiB of LDS, so at most one block is resident per CU and a grid of cu_count blocks on
+// an idle device can cover every CU. HIP promises nothing about placement: where a block ran is
+// read from the hardware registers and only *observed*; no result depends on it.
+//
+// CU id (12 bits) = XCC_ID[3:0] << 8 | HW_ID[15:8]; HW_ID[15:8] is CU_ID 11:8, SH_ID 12,
+// SE_ID 15:13 (2 bits on gfx942/950, the top bit reads 0); a wave's SIMD is HW_ID[5:4]. The id is
+// an attribution label taken from the registers, not something a result depends on.
+//
+// Every test gives 4 uint32 words per thread t (0..255), 1024 per block: word 4 t + i. They are a
+// pure function of (test, seed, iters, t), never of the block or its placement; the expected
+// table is computed on the host, uploaded once per scan and compared in the kernel. All integer
+// arithmetic is modulo 2^32. The code is gm_cuscan_sig.h (shared by the host and the kernel).
+//
+//   H(test, idx):  h = (u32)seed ^ (idx * 0x9E3779B1)
+//                  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13
+//                  h += (u32)(seed >> 32) ^ (test * 0xC2B2AE35)
+//                  h ^= h >> 16;  h *= 0xC2B2AE35;  h ^= h >> 13;  h *= 0x27D4EB2F;  h ^= h >> 16
+//
+//   GM_CUSCAN_VALU_INT 1   two chains (x0, y0), (x1, y1) = H(1, 4t), H(1, 4t+1), H(1, 4t+2),
+//                          H(1, 4t+3); for s in 0 .. 128 iters - 1, on both chains, with
+//                          k = (0x9E3779B9, 0x85EBCA6B, 0xC2B2AE35, 0x27D4EB2F)[s & 3]:
+//                            x = (rotl32(x, 24) + y) ^ k;   y = rotl32(y, 3) ^ x
+//                            m = (u64)x * (y | 1);   x ^= (u32)(m >> 32);   y += (u32)m
+//                          words x0, y0, x1, y1
+//   GM_CUSCAN_VALU_F32 2   four fp32 chains j = 0..3 with h1 = H(2, 4t+j), h2 = H(2, 1024+4t+j):
+//                            x = 1 + (h1 >> 9) / 2^23,  a = 1 + (h2 >> 20) / 2^12,
+//                            b = (h2 & 0xFFFFFF) / 2^24
+//                          for 64 iters steps: x = fmaf(x, a, b);  x = x - floorf(x) + 1
+//                          x * a + b needs fewer than 53 bits, so float32(float64(x) * a + b) is
+//                          the correctly rounded FMA; the range reduction is exact. Word j is the
+//                          bit pattern of chain j.
+//   GM_CUSCAN_MFMA     4   per wave w = t / 64: C_w = sum over s in 0 .. 4 iters - 1 of
+//                          A_{w,s} (16x32) . B_{w,s} (32x16) with v_mfma_f32_16x16x32_bf16, where
+//                            A[r][k] = E(H(4, ((4s + w) * 2 + 0) * 64 + r + 16 (k >> 3)), k & 7)
+//                            B[k][c] = E(H(4, ((4s + w) * 2 + 1) * 64 + c + 16 (k >> 3)), k & 7)
+//                            E(h, j) = ((h >> 4j) & 15) % 9 - 4           an integer in [-4, 4]
+//                          Every product and partial sum is an exact fp32 integer in any order
+//                          as long as 32 * 16 * steps < 2^24: iters <= 8191 (checked). Word i of
+//                          lane l = t % 64 is the fp32 bit pattern of C_w[4 (l >> 4) + i][l & 15],
+//                          the instruction's own accumulator layout.
+//   GM_CUSCAN_LDS      8   march over all 40960 words of the block's LDS, iters rounds r with
+//                          P(a) = H(8, 65536 r + a), s0 = s1 = s2 = s3 = 0 before the first:
+//                           1. thread t writes P to the 16-byte elements v = 256 k + t, k < 40
+//                              (words 4v .. 4v+3) with 128-bit stores; barrier
+//                           2. for i < 160: a = ((256 i + t) * 12347 + 7) % 40960 (a permutation
+//                              of the addresses: the stride is odd and no multiple of 5), 32-bit
+//                              read g of word a; s0 = rotl32(s0, 5) + g; s3 += (g != P(a));
+//                              32-bit write of ~g to word a; barrier
+//                           3. for k < 40: 128-bit read of element v = 256 k + (t + 64) % 256, and
+//                              for each of its words g, c = 0..3: s1 = rotl32(s1, 7) ^ g;
+//                              s2 += g; s3 += (g != ~P(4v + c)); barrier
+//                          words s0, s1, s2, s3 (s3 = mismatches seen in flight, expected 0).
+//                          Every word is written and read in both polarities. The element read
+//                          in phase 3 was first written by the next wave; of the permuted reads
+//                          of phase 2 about three in four are of a word another wave wrote.
+//
+// What the scan cannot see: transcendental units, register-file addressing, clocks, thermals.
+// The GM_CUSCAN_* test bits and the iters limits are defined in gm_cuscan_sig.h.
+#define GM_CUSCAN_MAX_RECORDS 16
+#define GM_CUSCAN_IDS 4096
+#define GM_CUSCAN_ANY 0xFFFFFFFFu
+
+typedef struct gm_cuscan_record {
+  uint32_t id;        // CU id the block ran on
+  uint32_t simd;      // SIMD of the wave that computed the word
+  uint32_t test;      // GM_CUSCAN_* bit
+  uint32_t thread;    // 0..255
+  uint32_t word;      // 0..3
+  uint32_t expected;
+  uint32_t got;
+  uint32_t pad;
+} gm_cuscan_record_t;
+
+// Negative control, a data flip: in every block that runs on a CU whose id is `id` (any CU with
+// GM_CUSCAN_ANY), `mask` (nonzero) is XORed into word `word` of thread `thread` of `test`'s
+// computed signature before the compare.
+typedef struct gm_cuscan_inject {
+  uint32_t id, test, thread, word, mask;
+} gm_cuscan_inject_t;
+
+typedef struct gm_cuscan_cu {
+  uint32_t id, xcc, se, sh, cu;
+  uint32_t runs;          // blocks that ran here
+  uint32_t failed_runs;   // of which had a wrong word
+  uint32_t tests_failed;  // mask of GM_CUSCAN_* bits
+  uint32_t simds_seen;    // mask of the SIMDs that waves of those blocks ran on
+  uint32_t simds_failed;  // mask of the SIMDs whose wave had a wrong word
+} gm_cuscan_cu_t;
+
+typedef struct gm_cuscan_result {
+  uint32_t cus_expected;    // multiProcessorCount
+  uint32_t cus_seen;        // distinct ids; > cus_expected would mean the id holds a bit that is
+                            // not a location: reported, never hidden
+  uint32_t complete;        // cus_seen == cus_expected
+  uint32_t rounds;
+  uint64_t blocks_run;
+  uint64_t words_in_error;
+  uint64_t blocks_four_simds;  // blocks whose four waves reported four distinct SIMDs
+  uint32_t failed_cus;
+  uint32_t records_filled;  // <= GM_CUSCAN_MAX_RECORDS; later wrong words are counted only
+  uint32_t xcc_cus[16];     // distinct ids per XCC
+  gm_cuscan_record_t records[GM_CUSCAN_MAX_RECORDS];
+  double seconds;           // wall time of the whole call
+  double kernel_ms;         // the rounds' kernels alone, summed (event pairs)
+} gm_cuscan_result_t;
+
+// out[4 t + i] = word i of thread t. Host only, needs no GPU. `test` one GM_CUSCAN_* bit,
+// 1 <= iters <= GM_CUSCAN_MAX_ITERS (GM_CUSCAN_MFMA_MAX_ITERS for the MFMA test).
+int gm_probe_cuscan_expected(uint32_t test, uint64_t seed, uint32_t iters, uint32_t* out);
+// Exactly one block of the scan's device code on the current device, which writes the raw
+// signature of `test` to dev_out (1024 uint32, 16-byte aligned) instead of comparing it, and to
+// dev_where (5 uint32) the CU id, then the four waves' SIMD ids. Asynchronous on `stream`.
+int gm_probe_cuscan_signature(uint32_t test, uint64_t seed, uint32_t iters, uint32_t* dev_out,
+                              uint32_t* dev_where, void* stream);
+// The scan of device `dev`. A round is one launch of cu_count blocks followed by a read of the
+// distinct-id counter; the scan stops after min_rounds once every CU has been seen, or at
+// max_rounds (1 <= min_rounds <= max_rounds <= 1024). `cus` (cus_cap entries, may be NULL with
+// cus_cap 0) receives one entry per CU seen, sorted by id; *n_cus (may be NULL) how many there are,
+// which may exceed cus_cap. Bad arguments, among them an injection whose test is not in
+// tests_mask: hipErrorInvalidValue before any HIP call.
+int gm_probe_cuscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed, int min_rounds,
+                    int max_rounds, const gm_cuscan_inject_t* inject, gm_cuscan_result_t* out,
+                    gm_cuscan_cu_t* cus, int cus_cap, int* n_cus);
+
 #ifdef __cplusplus
 }
 #endif
