@@ -267,6 +267,34 @@ class CuscanResult(C.Structure):
                 ("seconds", C.c_double), ("kernel_ms", C.c_double)]
 
 
+HOSTLINK_LEGS = 6             # native/include/gm_probe.h GM_HOSTLINK_LEGS
+HOSTLINK_MAX_RECORDS = 16     # GM_HOSTLINK_MAX_RECORDS
+HOSTLINK_MAX_BLOCKS = 1024    # GM_HOSTLINK_MAX_BLOCKS
+
+
+class HostlinkLeg(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("ms", C.c_double), ("gbps", C.c_double),
+                ("words_in_error", C.c_uint64)]
+
+
+class HostlinkRecord(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("expected", C.c_uint64), ("got", C.c_uint64),
+                ("leg", C.c_uint32), ("pattern", C.c_uint32), ("pass_", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class HostlinkResult(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("pinned_bytes", C.c_uint64),
+                ("words_in_error", C.c_uint64), ("bit_errors", C.c_uint64),
+                ("stuck_mask", C.c_uint64), ("records_filled", C.c_uint32),
+                ("legs_run", C.c_uint32), ("legs", HostlinkLeg * HOSTLINK_LEGS),
+                ("bidir_h2d", HostlinkLeg), ("bidir_d2h", HostlinkLeg),
+                ("records", HostlinkRecord * HOSTLINK_MAX_RECORDS),
+                ("seconds", C.c_double), ("host_seconds", C.c_double),
+                ("transfer_seconds", C.c_double), ("setup_seconds", C.c_double),
+                ("stage", C.c_char * 16)]
+
+
 def _prefer_torch_hip_runtime() -> None:
     """A process can hold only one HIP runtime, and ``libamdhip64.so.7`` is resolved by soname:
     whichever copy is loaded first (ROCm's /opt/rocm/lib or the one PyTorch bundles) serves
@@ -346,6 +374,21 @@ def probe() -> C.CDLL:
                                         C.c_int, C.POINTER(CuscanInject),
                                         C.POINTER(CuscanResult), C.POINTER(CuscanCu), C.c_int,
                                         C.POINTER(C.c_int)]
+        lib.gm_probe_hostlink_geometry.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.gm_probe_hostlink_unroll.argtypes = [C.c_int]
+        lib.gm_probe_hostlink_kwrite.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,
+                                                 C.c_uint64, C.c_uint32, C.c_uint64, C.c_int,
+                                                 C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.gm_probe_hostlink_kread.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,
+                                                C.c_uint64, C.c_uint32, C.c_uint64, C.c_int,
+                                                C.c_void_p, C.POINTER(MemtestResult)]
+        lib.gm_probe_hostlink_kcopy.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                                C.c_int, C.c_uint64, C.c_uint32, C.c_uint64,
+                                                C.c_int, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                C.POINTER(MemtestResult)]
+        lib.gm_probe_hostlink.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int,
+                                          C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint64,
+                                          C.c_uint64, C.POINTER(HostlinkResult)]
         lib.gm_probe_strerror.argtypes = [C.c_int]
         lib.gm_probe_strerror.restype = C.c_char_p
         lib._gm_typed = True

@@ -12,12 +12,16 @@
                                        [--cu-scan] [--cu-scan-tests int,f32,mfma,lds]
                                        [--cu-scan-rounds N]                  # per-CU self-test
                                        [--cu-scan-inject ID|any:TEST:THREAD:WORD:MASK]
+                                       [--host-link [SIZE]] [--host-link-legs h2d,d2h,...]
+                                       [--host-link-patterns addr,random] [--host-link-blocks N]
+                                       [--host-link-flip LEG:OFFSET:MASK]    # host link (PCIe) test
     python -m gpumounter_amd add    --master URL --ns NS --pod P -n 2 [--entire] [--lease 3600]
     python -m gpumounter_amd remove --master URL --ns NS --pod P --uuid U [--uuid U2] [--force]
     python -m gpumounter_amd status --master URL --node NODE
     python -m gpumounter_amd bpf-dump --allow 226:128 --allow 511:0   # generated device program
     python -m gpumounter_amd doctor  [--json] [--skip-cluster] [--gpu [--burn-in 30]]  # preflight
                                      [--gpu --memtest [SIZE]] [--gpu --cu-scan]
+                                     [--gpu --host-link [SIZE]]
     python -m gpumounter_amd config-doc > docs/CONFIG.md   # every GM_* setting, from the source
 
 The reference ships only the two daemons and documents curl calls (QuickStart.md:41-92); the
@@ -193,6 +197,31 @@ def _cuscan_arg(kind):
     return conv
 
 
+HOSTLINK_AUTO = -1    # --host-link without a SIZE: the test's default size
+
+
+def _hostlink_arg(kind):
+    """argparse type for the --host-link-* options: the parser in ops.hostlink, its refusal a
+    usage error."""
+    def conv(text):
+        from gpumounter_amd.ops import hostlink
+        try:
+            return getattr(hostlink, kind)(text)
+        except hostlink.ProbeError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    conv.__name__ = kind
+    return conv
+
+
+def _hostlink_bytes(size: int) -> Optional[int]:
+    return None if size == HOSTLINK_AUTO else size
+
+
+def _add_hostlink_size(p, what: str) -> None:
+    p.add_argument("--host-link", nargs="?", const=HOSTLINK_AUTO, default=None, metavar="SIZE",
+                   type=_hostlink_arg("parse_size"), help=what)
+
+
 def _add_memtest_size(p, what: str) -> None:
     p.add_argument("--memtest", nargs="?", const=MEMTEST_AUTO, default=None, metavar="SIZE",
                    type=_memtest_arg("parse_size"), help=what)
@@ -214,6 +243,32 @@ def cmd_probe(args) -> int:
         print(f"probe: --cu-scan-inject into {args.cu_scan_inject[1]!r}, which --cu-scan-tests "
               f"leaves out", file=sys.stderr)
         return 2
+    if args.host_link is None:
+        given = [o for o, v in (("--host-link-flip", args.host_link_flip),
+                                ("--host-link-legs", args.host_link_legs),
+                                ("--host-link-patterns", args.host_link_patterns),
+                                ("--host-link-blocks", args.host_link_blocks)) if v is not None]
+        if given:
+            print(f"probe: {given[0]} needs --host-link", file=sys.stderr)
+            return 2
+    else:
+        if args.host_link != HOSTLINK_AUTO and (args.host_link < 16 or args.host_link % 16):
+            print("probe: --host-link SIZE must be a nonzero multiple of 16 bytes",
+                  file=sys.stderr)
+            return 2
+        flip = args.host_link_flip
+        if flip and args.host_link_legs is not None and flip[0] not in args.host_link_legs:
+            print(f"probe: --host-link-flip into {flip[0]!r}, which --host-link-legs leaves out",
+                  file=sys.stderr)
+            return 2
+        if flip:
+            from gpumounter_amd.ops import hostlink as _hl
+
+            size = _hl.DEFAULT_BYTES if args.host_link == HOSTLINK_AUTO else args.host_link
+            if flip[1] + 8 > size:
+                print(f"probe: --host-link-flip offset {flip[1]} is outside the {size} bytes "
+                      f"tested", file=sys.stderr)
+                return 2
     if args.bdf:
         bdfs = args.bdf
     else:
@@ -241,6 +296,16 @@ def cmd_probe(args) -> int:
                                       max_rounds=max(16, args.cu_scan_rounds),
                                       _inject=args.cu_scan_inject)
             bad |= not r["cuscan"]["ok"]
+    if args.host_link is not None:
+        from gpumounter_amd.ops import hostlink
+
+        for r in res:
+            r["hostlink"] = hostlink.hostlink(
+                r["device"], _hostlink_bytes(args.host_link),
+                legs=args.host_link_legs or hostlink.ALL_LEGS,
+                patterns=args.host_link_patterns or hostlink.DEFAULT_PATTERNS,
+                blocks=args.host_link_blocks, _flip=args.host_link_flip)
+            bad |= not r["hostlink"]["ok"]
     print(json.dumps(res, indent=2))
     return 1 if bad else 0
 
@@ -395,10 +460,14 @@ def cmd_doctor(args) -> int:
 
     cfg = _cfg(args)
     memtest_bytes = args.memtest if args.memtest is not None else 0   # negative: automatic size
+    extra = {}
+    if args.host_link is not None:      # negative: the test's default size
+        extra["host_link_bytes"] = args.host_link
     checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
-                        gpu=args.gpu or bool(args.burn_in) or bool(memtest_bytes) or args.cu_scan,
+                        gpu=(args.gpu or bool(args.burn_in) or bool(memtest_bytes) or args.cu_scan
+                             or args.host_link is not None),
                         burn_in_s=args.burn_in, memtest_bytes=memtest_bytes,
-                        cu_scan=args.cu_scan)
+                        cu_scan=args.cu_scan, **extra)
     print(doctor.render(checks, args.json))
     return 1 if any(c.status == "fail" for c in checks) else 0
 
@@ -458,6 +527,19 @@ def build_parser() -> argparse.ArgumentParser:
                    metavar="ID|any:TEST:THREAD:WORD:MASK",
                    help="negative control: flip that signature word on that CU; the scan must "
                         "name it")
+    _add_hostlink_size(p, "host link (PCIe) test of every probed GPU over SIZE bytes of pinned "
+                          "host memory per buffer (default 256M): checked transfers in both "
+                          "directions by the copy engines and by kernels (exit 1 on any bad word)")
+    p.add_argument("--host-link-legs", type=_hostlink_arg("parse_legs"), default=None,
+                   metavar="a,b,...", help="of h2d,d2h,bidir,kread,kwrite,kduplex (default: all)")
+    p.add_argument("--host-link-patterns", type=_hostlink_arg("parse_patterns"), default=None,
+                   metavar="a,b,...", help="memtest patterns (default: addr,random)")
+    p.add_argument("--host-link-blocks", type=_hostlink_arg("parse_blocks"), default=None,
+                   metavar="N", help="grid of the kernel legs (1..1024)")
+    p.add_argument("--host-link-flip", type=_hostlink_arg("parse_flip"), default=None,
+                   metavar="LEG:OFFSET:MASK",
+                   help="negative control: one word of that leg's data arrives XORed with MASK; "
+                        "the leg must report it")
     p.set_defaults(fn=cmd_probe)
     for name, fn in (("add", cmd_add), ("remove", cmd_remove), ("status", cmd_status)):
         p = sub.add_parser(name)
@@ -497,6 +579,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "its free memory)")
     p.add_argument("--cu-scan", action="store_true",
                    help="with --gpu: per-CU self-test of every GPU; a failing CU is named")
+    _add_hostlink_size(p, "with --gpu: host link (PCIe) test of every GPU over SIZE bytes of "
+                          "pinned host memory per buffer (default 256M)")
     p.set_defaults(fn=cmd_doctor)
     p = sub.add_parser("bpf-dump")
     p.add_argument("--allow", action="append", default=[])

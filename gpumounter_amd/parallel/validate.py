@@ -16,7 +16,10 @@ starting a job on them — the reference offers nothing here:
    free on it, written and read back in both polarities of five patterns;
 6. optionally (``--cu-scan``) the per-CU self-test on all GPUs at once
    (:func:`gpumounter_amd.ops.cuscan.scan`): known-answer integer, fp32, MFMA and LDS tests on
-   every compute unit, a wrong word attributed to the CU that produced it.
+   every compute unit, a wrong word attributed to the CU that produced it;
+7. optionally (``--host-link [SIZE]``) the host link (PCIe) test on all GPUs at once
+   (:func:`gpumounter_amd.ops.hostlink.hostlink`): checked transfers between pinned host memory
+   and each GPU in both directions, by the copy engines and by kernels, with per-leg GB/s.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -82,7 +85,19 @@ def main(argv=None) -> int:
                          "(64M, 8G; default: 90 %% of the free memory)")
     ap.add_argument("--cu-scan", action="store_true",
                     help="then the per-CU self-test on every GPU at once")
+    ap.add_argument("--host-link", nargs="?", const="auto", default=None, metavar="SIZE",
+                    help="then the host link (PCIe) test on every GPU at once over SIZE bytes of "
+                         "pinned host memory per buffer (default 256M)")
     args = ap.parse_args(argv)
+    hostlink_bytes = None
+    if args.host_link not in (None, "auto"):
+        from gpumounter_amd.ops import hostlink
+        try:
+            hostlink_bytes = hostlink.parse_size(args.host_link)
+        except hostlink.ProbeError as e:
+            ap.error(str(e))
+        if hostlink_bytes < 16 or hostlink_bytes % 16:
+            ap.error("--host-link SIZE must be a nonzero multiple of 16 bytes")
     memtest_bytes = None
     if args.memtest not in (None, "auto"):
         from gpumounter_amd.ops import memtest
@@ -146,6 +161,16 @@ def main(argv=None) -> int:
             del c["per_cu"]               # one line per CU and GPU; "failed" names the bad ones
         report["cuscan"] = cs
         report["ok"] &= all(c["ok"] for c in cs)
+    if args.host_link is not None and not args.cpu_ranks:
+        from concurrent.futures import ThreadPoolExecutor
+
+        from gpumounter_amd.ops import hostlink
+
+        # all GPUs at once: they share the host's memory and, behind a switch, its upstream link
+        with ThreadPoolExecutor(max_workers=world) as ex:
+            hl = list(ex.map(lambda d: hostlink.hostlink(d, hostlink_bytes), range(world)))
+        report["hostlink"] = hl
+        report["ok"] &= all(h["ok"] for h in hl)
     print(json.dumps(report))
     return 0 if report["ok"] else 1
 

@@ -282,7 +282,8 @@ async def _check_priority(cfg, kube) -> List[Check]:
 
 def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                memtest_flip=None, burn_in_flip=None, cu_scan: bool = False,
-               cu_scan_inject=None) -> List[Check]:
+               cu_scan_inject=None, host_link_bytes: int = 0,
+               host_link_flip=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
@@ -291,7 +292,12 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     burn-in's (see :func:`probe.burn_in`). With ``cu_scan`` also the per-CU self-test
     (:func:`gpumounter_amd.ops.cuscan.scan`): a CU with a wrong word fails the check and is named;
     a scan that did not reach every CU is stated and does not fail it; ``cu_scan_inject`` is its
-    negative control. A GPU that fails here should not be handed out."""
+    negative control. With ``host_link_bytes`` also the host link (PCIe) test
+    (:func:`gpumounter_amd.ops.hostlink.hostlink`) over that many bytes of pinned host memory per
+    buffer (negative: its default size): a wrong word or a refused pin fails the check, a link
+    that stayed below its maximum speed or width under load is a warning; ``host_link_flip`` =
+    (leg, offset, mask) is its negative control. A GPU that fails here should not be handed
+    out."""
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import probe
 
@@ -342,6 +348,26 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                 if not c["ok"]:
                     detail += f", failed: {cuscan.describe_failed(c)}"
                     status = "fail"
+            if host_link_bytes:
+                from gpumounter_amd.ops import hostlink
+
+                try:
+                    h = hostlink.hostlink(d, host_link_bytes if host_link_bytes > 0 else None,
+                                          _flip=host_link_flip)
+                except hostlink.HostlinkError as e:
+                    detail += f", host-link failed: {e}"
+                    status = "fail"
+                else:
+                    rates = " ".join(f"{n} {leg['gbps']:.1f}" for n, leg in h["legs"].items())
+                    detail += (f", host-link {h['bytes'] / 2**20:.0f} MiB GB/s {rates}, "
+                               f"{h['errors']} wrong words")
+                    if not h["ok"]:
+                        detail += f", failed: {hostlink.describe_errors(h)}"
+                        status = "fail"
+                    if h["link"]["degraded"]:
+                        detail += (f", link below its maximum under load: "
+                                   f"{hostlink.describe_link(h['link'])}")
+                        status = "warn" if status == "ok" else status
             out.append(Check(f"gpu{d}", status, detail))
         except Exception as e:  # noqa: BLE001 - a faulting GPU is exactly what this finds
             out.append(Check(f"gpu{d}", "fail", f"probe failed: {e}"))
@@ -352,11 +378,14 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
 
 
 def run(cfg, skip_cluster: bool = False, gpu: bool = False,
-        burn_in_s: float = 0.0, *, memtest_bytes: int = 0, cu_scan: bool = False) -> List[Check]:
+        burn_in_s: float = 0.0, *, memtest_bytes: int = 0, cu_scan: bool = False,
+        host_link_bytes: int = 0) -> List[Check]:
     checks = check_inventory(cfg) + check_cgroup(cfg) + check_devnodes(cfg) + \
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
         extra = {"cu_scan": True} if cu_scan else {}
+        if host_link_bytes:
+            extra["host_link_bytes"] = host_link_bytes
         checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes, **extra)
     if not skip_cluster:
         async def both():

@@ -309,6 +309,119 @@ int gm_probe_cuscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed,
                     int max_rounds, const gm_cuscan_inject_t* inject, gm_cuscan_result_t* out,
                     gm_cuscan_cu_t* cus, int cus_cap, int* n_cus);
 
+// ------------------------------------------------------------------ host link (PCIe) test
+// Moves checked bytes between pinned host memory and the GPU, in both directions, by the copy
+// engines (hipMemcpyAsync) and by kernels that read and write host memory through its device
+// mapping. Every expected value is the memtest pattern function above (same patterns, seed, pass,
+// 64-bit global byte offset, inverted polarity); errors are reported in a gm_memtest_result_t.
+//
+// Kernel geometry (gm_hostlink.hip): `blocks` blocks (1..GM_HOSTLINK_MAX_BLOCKS) of 256 threads,
+// 16-byte elements, a contiguous chunk per block rounded up to whole steps of U * 256 elements
+// (U = 4 or 8 loads in flight per lane; gm_probe_hostlink_geometry reports the step in bytes), a
+// 16-byte tail loop, nontemporal accesses, one wave-instruction = 1 KiB of contiguous host memory.
+//
+// Legs of the driver, one GM_HOSTLINK_* bit each:
+//   H2D     1   hipMemcpyAsync pinned -> device        checked on the device (memtest verify)
+//   D2H     2   hipMemcpyAsync device -> pinned        checked on the host
+//   BIDIR   4   both at once on two streams, each to its own destination; both checks
+//   KREAD   8   kernel reads pinned memory             checked in the kernel
+//   KWRITE  16  kernel writes pinned memory            checked on the host
+//   KDUPLEX 32  kernel copies pinned -> pinned         checked in the kernel (source) and on the
+//                                                      host (destination)
+// Struct layout (checked by tests/test_hostlink.py): sizeof(gm_hostlink_leg_t) = 32,
+// sizeof(gm_hostlink_record_t) = 40, sizeof(gm_hostlink_result_t) = 992 with legs at byte 48,
+// bidir_h2d at 240, records at 304, seconds at 944 and stage at 976.
+#define GM_HOSTLINK_H2D 1
+#define GM_HOSTLINK_D2H 2
+#define GM_HOSTLINK_BIDIR 4
+#define GM_HOSTLINK_KREAD 8
+#define GM_HOSTLINK_KWRITE 16
+#define GM_HOSTLINK_KDUPLEX 32
+#define GM_HOSTLINK_ALL 63
+#define GM_HOSTLINK_LEGS 6
+#define GM_HOSTLINK_MAX_BLOCKS 1024
+#define GM_HOSTLINK_MAX_RECORDS 16
+
+typedef struct gm_hostlink_leg {
+  uint64_t bytes;           // bytes the timed transfers moved (both directions where there are two)
+  double ms;                // their time (device events), summed over patterns and passes
+  double gbps;              // bytes / ms
+  uint64_t words_in_error;
+} gm_hostlink_leg_t;
+
+typedef struct gm_hostlink_record {
+  uint64_t offset;          // byte offset of the word in the buffer
+  uint64_t expected;
+  uint64_t got;
+  uint32_t leg;             // GM_HOSTLINK_* bit
+  uint32_t pattern;         // GM_MEMTEST_* bit
+  uint32_t pass;
+  uint32_t pad;
+} gm_hostlink_record_t;
+
+typedef struct gm_hostlink_result {
+  uint64_t bytes;           // size of each of the four buffers
+  uint64_t pinned_bytes;    // pinned host memory held (two buffers)
+  uint64_t words_in_error;
+  uint64_t bit_errors;      // sum of popcount(expected ^ got)
+  uint64_t stuck_mask;      // OR of expected ^ got
+  uint32_t records_filled;  // <= GM_HOSTLINK_MAX_RECORDS; later wrong words are counted only
+  uint32_t legs_run;        // mask of the legs that ran to their end
+  gm_hostlink_leg_t legs[GM_HOSTLINK_LEGS];  // index = log2 of the leg's bit; BIDIR: both
+                                             // directions' bytes over their common window
+  gm_hostlink_leg_t bidir_h2d;  // BIDIR's directions on their own (words_in_error: that side's)
+  gm_hostlink_leg_t bidir_d2h;
+  gm_hostlink_record_t records[GM_HOSTLINK_MAX_RECORDS];
+  double seconds;           // wall time of the whole call
+  double host_seconds;      // of which host fill, poison and compare
+  double transfer_seconds;  // of which the transfers (warm-ups included) and the device checks
+  double setup_seconds;     // of which allocating and pinning the buffers, streams and events
+  char stage[16];           // what failed when the call returns an error: "args", "device",
+                            // "pin", "alloc", "setup" or a leg's name; "" on success
+} gm_hostlink_result_t;
+
+// *step_bytes: bytes per block per unrolled step (U * 256 * 16); *default_blocks: the grid the
+// driver uses for blocks = 0. Host only, needs no GPU. Either pointer may be NULL.
+int gm_probe_hostlink_geometry(uint32_t* step_bytes, uint32_t* default_blocks);
+// Tuning hook: 4 or 8 selects the kernels' loads in flight per lane (U). Returns the previous
+// setting; any other value only queries.
+int gm_probe_hostlink_unroll(int u);
+// Kernels on caller-owned pinned host memory, on the current device. Pointers 16-byte aligned,
+// `bytes` a nonzero multiple of 16, `base_offset` a multiple of 8, `pattern` one GM_MEMTEST_* bit,
+// 1 <= blocks <= GM_HOSTLINK_MAX_BLOCKS, flip_offset a multiple of 8, src and dst disjoint:
+// anything else is hipErrorInvalidValue before any HIP call. Then hipPointerGetAttributes must
+// call the first and the last byte host memory that the device can reach, and the address the
+// kernel uses is hipHostGetDevicePointer's; a device pointer or pageable memory is
+// hipErrorInvalidValue (or the HIP error) and nothing is launched. One launch each, asynchronous
+// on `stream` (may be NULL), except that kread and kcopy wait for their result.
+// flip_mask != 0: the 64-bit word written at global byte offset flip_offset (base_offset + local
+// offset) is XORed with flip_mask; what kcopy checks of its source is not affected.
+int gm_probe_hostlink_kwrite(void* host_ptr, uint64_t bytes, uint32_t pattern, int invert,
+                             uint64_t seed, uint32_t pass, uint64_t base_offset, int blocks,
+                             uint64_t flip_offset, uint64_t flip_mask, void* stream);
+// Only the error fields and bytes_tested of *out are set.
+int gm_probe_hostlink_kread(const void* host_ptr, uint64_t bytes, uint32_t pattern, int invert,
+                            uint64_t seed, uint32_t pass, uint64_t base_offset, int blocks,
+                            void* stream, gm_memtest_result_t* out);
+int gm_probe_hostlink_kcopy(const void* src_host, void* dst_host, uint64_t bytes, uint32_t pattern,
+                            int invert, uint64_t seed, uint32_t pass, uint64_t base_offset,
+                            int blocks, uint64_t flip_offset, uint64_t flip_mask, void* stream,
+                            gm_memtest_result_t* out);
+// The driver: two pinned (mapped, coherent) host buffers and two device buffers of `bytes` on
+// `dev`. For each pattern of pattern_mask and each of `passes` it runs the legs of legs_mask;
+// before a leg its destination holds the opposite polarity (device) or a poison fill (host), so a
+// transfer that did nothing cannot pass. Only the transfers are timed (device events, `iters`
+// repeats, 1..1024, after one warm-up of the same shape). blocks = 0: the default grid.
+// flip_mask != 0 is the negative control: one 64-bit word of flip_leg's data (one GM_HOSTLINK_*
+// bit of legs_mask) at byte offset flip_offset (multiple of 8, inside `bytes`) arrives XORed with
+// flip_mask: the host source is flipped for H2D, KREAD and BIDIR (its H2D half), the device
+// source for D2H (through a host round trip), and the kernel's flip argument is used for KWRITE
+// and KDUPLEX. Bad arguments: hipErrorInvalidValue before any HIP call. A failed pinned
+// allocation returns its HIP error with stage "pin".
+int gm_probe_hostlink(int dev, uint64_t bytes, uint32_t legs_mask, uint32_t pattern_mask,
+                      int passes, int iters, int blocks, uint64_t seed, uint32_t flip_leg,
+                      uint64_t flip_offset, uint64_t flip_mask, gm_hostlink_result_t* out);
+
 #ifdef __cplusplus
 }
 #endif
