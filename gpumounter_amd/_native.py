@@ -295,6 +295,48 @@ class HostlinkResult(C.Structure):
                 ("stage", C.c_char * 16)]
 
 
+ATOMICS_KINDS = 13            # native/include/gm_probe.h GM_ATOMICS_NKINDS
+ATOMICS_MAX_RECORDS = 16      # GM_ATOMICS_MAX_RECORDS
+ATOMICS_XCC_UNKNOWN = 0xFFFFFFFF
+
+
+class AtomicsKind(C.Structure):
+    _fields_ = [("ops", C.c_uint64), ("words_in_error", C.c_uint64), ("ms", C.c_double),
+                ("gops", C.c_double), ("width", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class AtomicsRecord(C.Structure):
+    _fields_ = [("index", C.c_uint64), ("expected", C.c_uint64), ("got", C.c_uint64),
+                ("test", C.c_uint32), ("kind", C.c_uint32), ("xcc_producer", C.c_uint32),
+                ("xcc_consumer", C.c_uint32)]
+
+
+class AtomicsInject(C.Structure):
+    _fields_ = [("test", C.c_uint32), ("kind", C.c_uint32), ("a", C.c_uint32),
+                ("b", C.c_uint32), ("word", C.c_uint32), ("mask", C.c_uint32)]
+
+
+class AtomicsResult(C.Structure):
+    _fields_ = [("tests_run", C.c_uint32), ("blocks", C.c_uint32), ("iters", C.c_uint32),
+                ("spread", C.c_uint32), ("rounds", C.c_uint32), ("lines", C.c_uint32),
+                ("budget_us", C.c_uint32), ("xccs_seen", C.c_uint32),
+                ("kinds", AtomicsKind * ATOMICS_KINDS),
+                ("words_in_error", C.c_uint64),
+                ("tickets", C.c_uint64), ("holes", C.c_uint64), ("duplicates", C.c_uint64),
+                ("counter_errors", C.c_uint64), ("order_violations", C.c_uint64),
+                ("out_of_range", C.c_uint64), ("cas_giveups", C.c_uint64),
+                ("handoffs", C.c_uint64), ("observed", C.c_uint64),
+                ("observed_cross_xcc", C.c_uint64), ("unseen", C.c_uint64),
+                ("stale_words", C.c_uint64), ("lost_words", C.c_uint64),
+                ("poll_max_us", C.c_double), ("poll_mean_us", C.c_double),
+                ("pairs_observed", (C.c_uint32 * 16) * 16),
+                ("pairs_stale", (C.c_uint32 * 16) * 16),
+                ("xcc_blocks", C.c_uint32 * 16),
+                ("records_filled", C.c_uint32), ("pad", C.c_uint32),
+                ("records", AtomicsRecord * ATOMICS_MAX_RECORDS),
+                ("seconds", C.c_double)]
+
+
 def _prefer_torch_hip_runtime() -> None:
     """A process can hold only one HIP runtime, and ``libamdhip64.so.7`` is resolved by soname:
     whichever copy is loaded first (ROCm's /opt/rocm/lib or the one PyTorch bundles) serves
@@ -389,6 +431,30 @@ def probe() -> C.CDLL:
         lib.gm_probe_hostlink.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int,
                                           C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint64,
                                           C.c_uint64, C.POINTER(HostlinkResult)]
+        lib.gm_probe_atomics_expected.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_uint64, C.c_void_p, C.c_uint64]
+        lib.gm_probe_atomics_widths.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_uint64)]
+        lib.gm_probe_atomics_payload.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.gm_probe_atomics_payload.restype = C.c_uint32
+        lib.gm_probe_atomics_add.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint64, C.POINTER(AtomicsInject),
+                                             C.c_void_p]
+        lib.gm_probe_atomics_cas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint64, C.POINTER(AtomicsInject),
+                                             C.c_void_p, C.POINTER(AtomicsResult)]
+        lib.gm_probe_atomics_ticket.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                C.POINTER(AtomicsInject), C.c_void_p,
+                                                C.POINTER(AtomicsResult)]
+        lib.gm_probe_atomics_handoff.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                 C.c_uint32, C.c_uint32, C.c_uint64,
+                                                 C.POINTER(AtomicsInject), C.c_void_p,
+                                                 C.POINTER(AtomicsResult)]
+        lib.gm_probe_atomics.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                         C.POINTER(AtomicsInject), C.POINTER(AtomicsResult)]
         lib.gm_probe_strerror.argtypes = [C.c_int]
         lib.gm_probe_strerror.restype = C.c_char_p
         lib._gm_typed = True

@@ -15,13 +15,18 @@
                                        [--host-link [SIZE]] [--host-link-legs h2d,d2h,...]
                                        [--host-link-patterns addr,random] [--host-link-blocks N]
                                        [--host-link-flip LEG:OFFSET:MASK]    # host link (PCIe) test
+                                       [--atomics] [--atomics-tests add,ticket,cas,handoff]
+                                       [--atomics-spread N] [--atomics-blocks N]
+                                       [--atomics-rounds N]                  # cross-XCC atomics
+                                       [--atomics-inject add:KIND:G:S:MASK|cas:G:S:MASK|
+                                                         ticket:G:S|handoff:BLOCK:ROUND:WORD:MASK]
     python -m gpumounter_amd add    --master URL --ns NS --pod P -n 2 [--entire] [--lease 3600]
     python -m gpumounter_amd remove --master URL --ns NS --pod P --uuid U [--uuid U2] [--force]
     python -m gpumounter_amd status --master URL --node NODE
     python -m gpumounter_amd bpf-dump --allow 226:128 --allow 511:0   # generated device program
     python -m gpumounter_amd doctor  [--json] [--skip-cluster] [--gpu [--burn-in 30]]  # preflight
                                      [--gpu --memtest [SIZE]] [--gpu --cu-scan]
-                                     [--gpu --host-link [SIZE]]
+                                     [--gpu --host-link [SIZE]] [--gpu --atomics]
     python -m gpumounter_amd config-doc > docs/CONFIG.md   # every GM_* setting, from the source
 
 The reference ships only the two daemons and documents curl calls (QuickStart.md:41-92); the
@@ -197,6 +202,27 @@ def _cuscan_arg(kind):
     return conv
 
 
+def _atomics_arg(kind):
+    """argparse type for the --atomics-* options: the parser in ops.atomics, its refusal a usage
+    error."""
+    def conv(text):
+        from gpumounter_amd.ops import atomics
+        try:
+            return getattr(atomics, kind)(text)
+        except atomics.ProbeError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    conv.__name__ = kind
+    return conv
+
+
+def _add_atomics(p, what: str) -> None:
+    p.add_argument("--atomics", action="store_true", help=what)
+    p.add_argument("--atomics-inject", type=_atomics_arg("parse_inject"), default=None,
+                   metavar="TEST:...",
+                   help="negative control: add:KIND:G:S:MASK, cas:G:S:MASK, ticket:G:S or "
+                        "handoff:BLOCK:ROUND:WORD:MASK; the test must report it")
+
+
 HOSTLINK_AUTO = -1    # --host-link without a SIZE: the test's default size
 
 
@@ -269,6 +295,31 @@ def cmd_probe(args) -> int:
                 print(f"probe: --host-link-flip offset {flip[1]} is outside the {size} bytes "
                       f"tested", file=sys.stderr)
                 return 2
+    if not args.atomics:
+        given = [o for o, v in (("--atomics-inject", args.atomics_inject),
+                                ("--atomics-tests", args.atomics_tests),
+                                ("--atomics-spread", args.atomics_spread),
+                                ("--atomics-blocks", args.atomics_blocks),
+                                ("--atomics-rounds", args.atomics_rounds)) if v is not None]
+        if given:
+            print(f"probe: {given[0]} needs --atomics", file=sys.stderr)
+            return 2
+    else:
+        from gpumounter_amd.ops import atomics as _at
+
+        if args.atomics_blocks is not None and not 1 <= args.atomics_blocks <= _at.MAX_BLOCKS:
+            print(f"probe: --atomics-blocks must be between 1 and {_at.MAX_BLOCKS}",
+                  file=sys.stderr)
+            return 2
+        if args.atomics_rounds is not None and not 1 <= args.atomics_rounds <= _at.MAX_ROUNDS:
+            print(f"probe: --atomics-rounds must be between 1 and {_at.MAX_ROUNDS}",
+                  file=sys.stderr)
+            return 2
+        inj = args.atomics_inject
+        if inj and args.atomics_tests is not None and inj[0] not in args.atomics_tests:
+            print(f"probe: --atomics-inject into {inj[0]!r}, which --atomics-tests leaves out",
+                  file=sys.stderr)
+            return 2
     if args.bdf:
         bdfs = args.bdf
     else:
@@ -306,6 +357,17 @@ def cmd_probe(args) -> int:
                 patterns=args.host_link_patterns or hostlink.DEFAULT_PATTERNS,
                 blocks=args.host_link_blocks, _flip=args.host_link_flip)
             bad |= not r["hostlink"]["ok"]
+    if args.atomics:
+        from gpumounter_amd.ops import atomics
+
+        for r in res:
+            r["atomics"] = atomics.run(
+                r["device"], tests=args.atomics_tests or atomics.ALL_TESTS,
+                blocks=args.atomics_blocks or 0,
+                spread=args.atomics_spread or atomics.DEFAULT_SPREAD,
+                rounds=args.atomics_rounds or atomics.DEFAULT_ROUNDS,
+                _inject=args.atomics_inject)
+            bad |= not r["atomics"]["ok"]
     print(json.dumps(res, indent=2))
     return 1 if bad else 0
 
@@ -463,9 +525,16 @@ def cmd_doctor(args) -> int:
     extra = {}
     if args.host_link is not None:      # negative: the test's default size
         extra["host_link_bytes"] = args.host_link
+    if args.atomics_inject and not args.atomics:
+        print("doctor: --atomics-inject needs --atomics", file=sys.stderr)
+        return 2
+    if args.atomics:
+        extra["atomics"] = True
+        if args.atomics_inject:
+            extra["atomics_inject"] = args.atomics_inject
     checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
                         gpu=(args.gpu or bool(args.burn_in) or bool(memtest_bytes) or args.cu_scan
-                             or args.host_link is not None),
+                             or args.host_link is not None or args.atomics),
                         burn_in_s=args.burn_in, memtest_bytes=memtest_bytes,
                         cu_scan=args.cu_scan, **extra)
     print(doctor.render(checks, args.json))
@@ -540,6 +609,18 @@ def build_parser() -> argparse.ArgumentParser:
                    metavar="LEG:OFFSET:MASK",
                    help="negative control: one word of that leg's data arrives XORed with MASK; "
                         "the leg must report it")
+    _add_atomics(p, "cross-XCC atomics and coherence test of every probed GPU: known-answer "
+                    "atomics, tickets, a CAS loop and in-launch hand-offs between blocks (exit 1 "
+                    "on any wrong word, lost or doubled ticket)")
+    p.add_argument("--atomics-tests", type=_atomics_arg("parse_tests"), default=None,
+                   metavar="a,b,...", help="of add,ticket,cas,handoff (default: all)")
+    p.add_argument("--atomics-spread", type=_atomics_arg("parse_spread"), default=None,
+                   metavar="N", help="words per table and ticket counters, a power of two "
+                                     "1..65536 (default 4096; 1 is one hot word)")
+    p.add_argument("--atomics-blocks", type=int, default=None, metavar="N",
+                   help="blocks of 256 threads, 1..4096 (default: one per CU)")
+    p.add_argument("--atomics-rounds", type=int, default=None, metavar="N",
+                   help="hand-off rounds, 1..64 (default 8)")
     p.set_defaults(fn=cmd_probe)
     for name, fn in (("add", cmd_add), ("remove", cmd_remove), ("status", cmd_status)):
         p = sub.add_parser(name)
@@ -581,6 +662,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --gpu: per-CU self-test of every GPU; a failing CU is named")
     _add_hostlink_size(p, "with --gpu: host link (PCIe) test of every GPU over SIZE bytes of "
                           "pinned host memory per buffer (default 256M)")
+    _add_atomics(p, "with --gpu: cross-XCC atomics and coherence test of every GPU")
     p.set_defaults(fn=cmd_doctor)
     p = sub.add_parser("bpf-dump")
     p.add_argument("--allow", action="append", default=[])

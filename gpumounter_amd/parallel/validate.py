@@ -19,7 +19,10 @@ starting a job on them — the reference offers nothing here:
    every compute unit, a wrong word attributed to the CU that produced it;
 7. optionally (``--host-link [SIZE]``) the host link (PCIe) test on all GPUs at once
    (:func:`gpumounter_amd.ops.hostlink.hostlink`): checked transfers between pinned host memory
-   and each GPU in both directions, by the copy engines and by kernels, with per-leg GB/s.
+   and each GPU in both directions, by the copy engines and by kernels, with per-leg GB/s;
+8. optionally (``--atomics``) the cross-XCC atomics and coherence test on all GPUs at once
+   (:func:`gpumounter_amd.ops.atomics.run`): known-answer atomics of ten kinds, tickets, a CAS
+   loop and in-launch hand-offs between blocks with the agent-scope release and acquire.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -88,7 +91,20 @@ def main(argv=None) -> int:
     ap.add_argument("--host-link", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the host link (PCIe) test on every GPU at once over SIZE bytes of "
                          "pinned host memory per buffer (default 256M)")
+    ap.add_argument("--atomics", action="store_true",
+                    help="then the cross-XCC atomics and coherence test on every GPU at once")
+    ap.add_argument("--atomics-inject", default=None, metavar="TEST:...",
+                    help="its negative control (see probe --atomics-inject); needs --atomics")
     args = ap.parse_args(argv)
+    atomics_inject = None
+    if args.atomics_inject is not None:
+        from gpumounter_amd.ops import atomics
+        if not args.atomics:
+            ap.error("--atomics-inject needs --atomics")
+        try:
+            atomics_inject = atomics.parse_inject(args.atomics_inject)
+        except atomics.ProbeError as e:
+            ap.error(str(e))
     hostlink_bytes = None
     if args.host_link not in (None, "auto"):
         from gpumounter_amd.ops import hostlink
@@ -171,6 +187,18 @@ def main(argv=None) -> int:
             hl = list(ex.map(lambda d: hostlink.hostlink(d, hostlink_bytes), range(world)))
         report["hostlink"] = hl
         report["ok"] &= all(h["ok"] for h in hl)
+    if args.atomics and not args.cpu_ranks:
+        from concurrent.futures import ThreadPoolExecutor
+
+        from gpumounter_amd.ops import atomics
+
+        with ThreadPoolExecutor(max_workers=world) as ex:
+            at = list(ex.map(lambda d: atomics.run(d, _inject=atomics_inject), range(world)))
+        for a in at:
+            del a["pairs_stale"]          # 256 zeros per GPU unless something failed:
+            #                               "first_errors" names the XCCs then
+        report["atomics"] = at
+        report["ok"] &= all(a["ok"] for a in at)
     print(json.dumps(report))
     return 0 if report["ok"] else 1
 

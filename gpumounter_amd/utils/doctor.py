@@ -283,7 +283,8 @@ async def _check_priority(cfg, kube) -> List[Check]:
 def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                memtest_flip=None, burn_in_flip=None, cu_scan: bool = False,
                cu_scan_inject=None, host_link_bytes: int = 0,
-               host_link_flip=None) -> List[Check]:
+               host_link_flip=None, atomics: bool = False,
+               atomics_inject=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
@@ -296,8 +297,12 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     (:func:`gpumounter_amd.ops.hostlink.hostlink`) over that many bytes of pinned host memory per
     buffer (negative: its default size): a wrong word or a refused pin fails the check, a link
     that stayed below its maximum speed or width under load is a warning; ``host_link_flip`` =
-    (leg, offset, mask) is its negative control. A GPU that fails here should not be handed
-    out."""
+    (leg, offset, mask) is its negative control. With ``atomics`` also the cross-XCC atomics and
+    coherence test (:func:`gpumounter_amd.ops.atomics.run`): a wrong table word, a lost or doubled
+    ticket, a given-up CAS or a stale or lost hand-off word fails the check and is named; hand-offs
+    not seen within the budget do not, but when none at all was seen the check warns that the
+    hand-off proved nothing; ``atomics_inject`` is its negative control. A GPU that fails here
+    should not be handed out."""
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import probe
 
@@ -368,6 +373,21 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                         detail += (f", link below its maximum under load: "
                                    f"{hostlink.describe_link(h['link'])}")
                         status = "warn" if status == "ok" else status
+            if atomics:
+                from gpumounter_amd.ops import atomics as at
+
+                a = at.run(d, _inject=atomics_inject)
+                detail += (f", atomics {'+'.join(a['tests'])} {a['blocks']} blocks on "
+                           f"{a['xccs_seen']} XCCs {a['seconds'] * 1e3:.0f} ms "
+                           f"{a['words_in_error']} wrong words, hand-offs "
+                           f"{a['observed']}/{a['handoffs']} seen "
+                           f"({a['observed_cross_xcc']} across XCCs)")
+                if not a["ok"]:
+                    detail += f", failed: {at.describe_failed(a)}"
+                    status = "fail"
+                elif a["handoff_vacuous"]:
+                    detail += ", no hand-off was seen within the budget: it proved nothing"
+                    status = "warn" if status == "ok" else status
             out.append(Check(f"gpu{d}", status, detail))
         except Exception as e:  # noqa: BLE001 - a faulting GPU is exactly what this finds
             out.append(Check(f"gpu{d}", "fail", f"probe failed: {e}"))
@@ -379,13 +399,17 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
 
 def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         burn_in_s: float = 0.0, *, memtest_bytes: int = 0, cu_scan: bool = False,
-        host_link_bytes: int = 0) -> List[Check]:
+        host_link_bytes: int = 0, atomics: bool = False, atomics_inject=None) -> List[Check]:
     checks = check_inventory(cfg) + check_cgroup(cfg) + check_devnodes(cfg) + \
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
         extra = {"cu_scan": True} if cu_scan else {}
         if host_link_bytes:
             extra["host_link_bytes"] = host_link_bytes
+        if atomics:
+            extra["atomics"] = True
+            if atomics_inject is not None:
+                extra["atomics_inject"] = atomics_inject
         checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes, **extra)
     if not skip_cluster:
         async def both():

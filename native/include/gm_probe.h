@@ -422,6 +422,191 @@ int gm_probe_hostlink(int dev, uint64_t bytes, uint32_t legs_mask, uint32_t patt
                       int passes, int iters, int blocks, uint64_t seed, uint32_t flip_leg,
                       uint64_t flip_offset, uint64_t flip_mask, gm_hostlink_result_t* out);
 
+// ------------------------------------------------------- cross-XCC atomics and coherence test
+// Checks what connects the XCCs: the memory-side atomic units behind the eight private L2s, and
+// the agent-scope release/acquire hand-off between blocks of one launch (gm_atomics.hip; value
+// functions and host reference: gm_atomics_ref.h, which also defines the GM_ATOMICS_* test bits,
+// the GM_ATOMICS_K_* kinds and the limits). No kernel waits without a bound on another block: the
+// known-answer tests do not wait at all, the CAS loop is bounded by a count a correct machine
+// cannot exceed, and the hand-off's poll by wall-clock time. No result depends on where a block
+// ran; XCC ids are read from HW_REG_XCC_ID and are attribution labels only.
+//
+// Geometry: `blocks` blocks (1..4096; 0 in the driver: multiProcessorCount) of 256 threads,
+// g = 256 block + t, T = 256 blocks, T * iters <= 2^26, iters <= 1024. Every shared word is
+// accessed with __hip_atomic_* at agent scope, relaxed unless stated, and is set by a
+// hipMemsetAsync on the call's stream before every launch. H is the CU scan's mixer:
+//   H(kind, g, s)  = H_cuscan(0x100 + kind, 1024 g + s)
+//   H'(kind, g, s) = H_cuscan(0x120 + kind, 1024 g + s)        upper half of a 64-bit operand
+//   a(g, s)        = (g + 97 s) mod W                          W a power of two
+//
+// GM_ATOMICS_ADD 1: for s < iters thread g applies one no-return operation to word a(g, s) of
+// the kind's own table of W words. The operations of a kind commute, so the host fold in any
+// order gives the final table exactly; a compare kernel checks it after the kernel boundary.
+//   kind 0 add u32   operand H                           table starts 0
+//        1 add u64   operand H' << 32 | H                0
+//        2 xor u64   the same                            0
+//        3 umax u32  H                                   0
+//        4 umin u32  H                                   0xFFFFFFFF
+//        5 and u32   ~B(H)                               0xFFFFFFFF
+//        6 or  u32   B(H)                                0
+//                    B(h) = 1 << (h & 31) if ((h >> 5) & 7) == 0, else 0: one bit in one
+//                    operation of eight, so a word takes about a thousand operations to saturate
+//        7 add f32   (float)(H % 9 - 4)                  +0.0    exact while 4 adds < 2^24
+//        8 add f64   (double)(H % 9 - 4)                 +0.0    the same cap
+//        9 packed bf16 add: low half H & 1, high half (H >> 1) & 1       at most 128 adds into a
+//                    word: every partial sum is an integer <= 256, exact in 8 significand bits
+// `spread` (a power of two, 1..65536) is the requested W. A kind with a cap uses the smallest
+// power of two >= spread at which the busiest word (counted, not estimated) stays within the cap;
+// for bf16 that is at least ceil(T iters / 128).
+//
+// GM_ATOMICS_TICKET 2: K = spread counters. For s < iters thread g draws
+// old = fetch_add(ctr[k], d), k = a(g, s) with W = K, d = 1 + (H(10, g, s) & 3), and adds 1 (no
+// return) to each of mark[k][old .. old + d). N_k, the host's final value of counter k, sizes
+// mark[k]; the marks of all counters lie one after another. The audit kernel counts holes (a mark
+// of 0), duplicates (a mark above 1) and counter_errors (ctr[k] != N_k); the draw kernel counts
+// out_of_range (a ticket at or above N_k, which is not marked) and, for K <= 16, order_violations
+// (a thread's tickets from one counter must strictly increase; for larger K a thread returns to a
+// counter only after K draws and the order is not tracked).
+//
+// GM_ATOMICS_CAS 4: add u64 (operand as kind 1, with kind 11's hashes) through a compare-exchange
+// loop. A thread gives up an operation, and stops, after as many failed exchanges as the host
+// counted operations into that word: cas_giveups must be 0. The retries grow with the square of
+// the operations into a word, so the table is widened, as for the float kinds, until no word
+// takes more than 1024.
+//
+// GM_ATOMICS_HANDOFF 8: mailbox (b, r) is `lines` x 4 KiB of payload (lines 1 or 16; thread t
+// holds words 1024 l + 4 t .. + 3 of line l) and a flag word on a 128-byte line of its own;
+// E(b, r, word) = H_cuscan(0x10C, b << 20 | r << 14 | word). For r < rounds block b produces its
+// mailbox (plain 16-byte stores; every wave s_waitcnt vmcnt(0); barrier; lane 0: agent release
+// fence, s_waitcnt vmcnt(0), relaxed agent store of flag = own XCC id << 16 | r + 1) and then
+// consumes that of p = (b + 1 + r mod (G - 1)) mod G (p = b for G = 1): every thread first
+// plain-loads its payload bytes, so the lines are in its L1; lane 0 polls the flag with relaxed
+// agent loads until its low half reads r + 1 or wall_clock64() has advanced budget_us; seen: lane
+// 0's agent acquire fence, s_waitcnt vmcnt(0), barrier, then every thread plain-loads and
+// compares every word (stale_words); not seen: unseen += 1. After the launch an audit kernel
+// checks every payload word and flag again (lost_words).
+//
+// Negative controls (gm_atomics_inject_t, mask 0 / test 0: none):
+//   ADD, CAS   (kind, a = g, b = s, mask): H of that one operation is XORed with mask
+//   TICKET     (a = g, b = s): that draw marks its first slot twice
+//   HANDOFF    (a = block, b = round, word, mask): that payload word is stored XORed with mask
+//
+// Struct layout (checked by tests/test_atomics.py): sizeof(gm_atomics_kind_t) = 40,
+// sizeof(gm_atomics_record_t) = 40, sizeof(gm_atomics_inject_t) = 24,
+// sizeof(gm_atomics_result_t) = 3448 with kinds at byte 32, words_in_error at 552, tickets at
+// 560, cas_giveups at 608, handoffs at 616, poll_max_us at 664, pairs_observed at 680,
+// pairs_stale at 1704, xcc_blocks at 2728, records_filled at 2792, records at 2800 and seconds
+// at 3440.
+#define GM_ATOMICS_MAX_RECORDS 16
+#define GM_ATOMICS_NKINDS 13
+#define GM_ATOMICS_XCC_UNKNOWN 0xFFFFFFFFu
+
+typedef struct gm_atomics_kind {
+  uint64_t ops;             // operations done
+  uint64_t words_in_error;  // ADD kinds and CAS: table words that differ from the host's
+  double ms;                // the kind's kernel alone (event pair)
+  double gops;              // ops / ms
+  uint32_t width;           // table words (ADD, CAS), counters (TICKET), mailboxes (HANDOFF)
+  uint32_t pad;
+} gm_atomics_kind_t;
+
+typedef struct gm_atomics_record {
+  uint64_t index;           // table word; flat mark index, then the counters; HANDOFF: mailbox << 14 | word,
+                            // a flag: 1 << 40 | mailbox
+  uint64_t expected;
+  uint64_t got;
+  uint32_t test;            // GM_ATOMICS_* bit
+  uint32_t kind;            // GM_ATOMICS_K_*
+  uint32_t xcc_producer;    // HANDOFF: from the flag; GM_ATOMICS_XCC_UNKNOWN elsewhere
+  uint32_t xcc_consumer;    // HANDOFF, in-launch compare: the reading block's
+} gm_atomics_record_t;
+
+typedef struct gm_atomics_inject {
+  uint32_t test;            // one GM_ATOMICS_* bit
+  uint32_t kind;            // ADD: the kind 0..9; ignored elsewhere
+  uint32_t a, b;            // g, s or block, round
+  uint32_t word;            // HANDOFF: payload word < 1024 lines
+  uint32_t mask;            // nonzero except for TICKET
+} gm_atomics_inject_t;
+
+typedef struct gm_atomics_result {
+  uint32_t tests_run;       // mask of the tests that ran to their end
+  uint32_t blocks, iters, spread, rounds, lines, budget_us;
+  uint32_t xccs_seen;       // distinct XCC ids over the census launch
+  gm_atomics_kind_t kinds[GM_ATOMICS_NKINDS];
+  uint64_t words_in_error;  // ADD and CAS tables together
+  uint64_t tickets, holes, duplicates, counter_errors, order_violations, out_of_range;
+  uint64_t cas_giveups;
+  uint64_t handoffs, observed, observed_cross_xcc, unseen, stale_words, lost_words;
+  double poll_max_us, poll_mean_us;  // of observed hand-offs
+  uint32_t pairs_observed[16][16];   // [producer XCC][consumer XCC]
+  uint32_t pairs_stale[16][16];      // wrong words, booked the same way
+  uint32_t xcc_blocks[16];           // blocks of the census launch per XCC
+  uint32_t records_filled;  // <= GM_ATOMICS_MAX_RECORDS; later errors are counted only
+  uint32_t pad;
+  gm_atomics_record_t records[GM_ATOMICS_MAX_RECORDS];
+  double seconds;           // wall time of the whole call
+} gm_atomics_result_t;
+
+// The host's final table of one kind: GM_ATOMICS_K_* 0..11, or 13 (GM_ATOMICS_K_COUNT) for the
+// operations per word. `out` holds `width` words of 4 bytes, 8 for kinds 1, 2, 8 and 11;
+// out_bytes must say exactly that. TICKET: width = K, out = N_k. Host only, needs no GPU.
+// Refused (hipErrorInvalidValue): a bad geometry, a width that is no power of two or above 2^21,
+// and a width at which the kind's busiest word would break its exactness cap.
+int gm_probe_atomics_expected(uint32_t kind, uint32_t blocks, uint32_t iters, uint32_t width,
+                              uint64_t seed, void* out, uint64_t out_bytes);
+// widths[k], caps[k] (0: none) and max_adds[k] (operations into the busiest word at that width)
+// per kind for a configuration; TICKET's width is `spread`, HANDOFF's entries are 0.
+// Any pointer may be NULL. Host only. hipErrorInvalidValue for a bad geometry or spread, or when a
+// cap cannot be kept at any width.
+int gm_probe_atomics_widths(uint32_t blocks, uint32_t iters, uint32_t spread,
+                            uint32_t widths[GM_ATOMICS_NKINDS], uint64_t caps[GM_ATOMICS_NKINDS],
+                            uint64_t max_adds[GM_ATOMICS_NKINDS]);
+// E(b, r, word) of the hand-off. Host only.
+uint32_t gm_probe_atomics_payload(uint64_t seed, uint32_t block, uint32_t round, uint32_t word);
+// The tests on caller-owned hipMalloc memory of the current device, on `stream` (may be NULL).
+// Every buffer is set by hipMemsetAsync on the stream first. Bad arguments (geometry, alignment
+// to the word size, a width that breaks a cap, an injection outside the run): hipErrorInvalidValue
+// before any HIP call. add is asynchronous; the others wait for their counters and set only
+// their own fields of *out (and the records).
+//   add:     kind 0..9, dev_table of `width` words
+//   cas:     dev_table of `width` uint64; dev_bounds `width` uint32 holding the COUNT table
+//   ticket:  dev_ctr K uint32; dev_off K + 1 uint64, the prefix sums of N_k; dev_marks
+//            dev_off[K] = marks uint32
+//   handoff: dev_payload blocks * rounds * lines * 4096 bytes, 16-byte aligned; dev_flags
+//            blocks * rounds * 128 bytes
+int gm_probe_atomics_add(uint32_t kind, void* dev_table, uint32_t width, uint32_t blocks,
+                         uint32_t iters, uint64_t seed, const gm_atomics_inject_t* inject,
+                         void* stream);
+int gm_probe_atomics_cas(void* dev_table, const void* dev_bounds, uint32_t width, uint32_t blocks,
+                         uint32_t iters, uint64_t seed, const gm_atomics_inject_t* inject,
+                         void* stream, gm_atomics_result_t* out);
+int gm_probe_atomics_ticket(void* dev_ctr, const void* dev_off, void* dev_marks, uint64_t marks,
+                            uint32_t counters, uint32_t blocks, uint32_t iters, uint64_t seed,
+                            const gm_atomics_inject_t* inject, void* stream,
+                            gm_atomics_result_t* out);
+int gm_probe_atomics_handoff(void* dev_payload, void* dev_flags, uint32_t blocks, uint32_t rounds,
+                             uint32_t lines, uint32_t budget_us, uint64_t seed,
+                             const gm_atomics_inject_t* inject, void* stream,
+                             gm_atomics_result_t* out);
+// The driver: the tests of tests_mask on device `dev` with its own buffers, on the default
+// stream. blocks = 0: multiProcessorCount. `inject` (may be NULL) must name a test of tests_mask
+// and a place inside the run. Bad arguments: hipErrorInvalidValue before any HIP call (with
+// blocks = 0, what depends on the block count is checked once the device has been asked).
+int gm_probe_atomics(int dev, uint32_t tests_mask, uint32_t blocks, uint32_t iters,
+                     uint32_t spread, uint32_t rounds, uint32_t lines, uint32_t budget_us,
+                     uint64_t seed, const gm_atomics_inject_t* inject, gm_atomics_result_t* out);
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(gm_atomics_kind_t) == 40 && sizeof(gm_atomics_record_t) == 40 &&
+                  sizeof(gm_atomics_inject_t) == 24 && sizeof(gm_atomics_result_t) == 3448,
+              "gm_atomics_* layout");
+static_assert(__builtin_offsetof(gm_atomics_result_t, kinds) == 32 &&
+                  __builtin_offsetof(gm_atomics_result_t, tickets) == 560 &&
+                  __builtin_offsetof(gm_atomics_result_t, handoffs) == 616 &&
+                  __builtin_offsetof(gm_atomics_result_t, pairs_observed) == 680 &&
+                  __builtin_offsetof(gm_atomics_result_t, records) == 2800 &&
+                  __builtin_offsetof(gm_atomics_result_t, seconds) == 3440,
+              "gm_atomics_result_t layout");
 #endif
