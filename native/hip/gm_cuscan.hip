@@ -14,7 +14,6 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include <chrono>
 #include <vector>
 
 #include "gm_cuscan_sig.h"
@@ -275,9 +274,9 @@ int gm_probe_cuscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed,
     return (int)hipErrorInvalidValue;
   DeviceGuard g(dev);
   if (!g.ok) return (int)hipErrorInvalidDevice;
-  const auto t0 = std::chrono::steady_clock::now();
+  const double t0 = now_s();
   int cu_count = 0;
-  GM_CHECK(hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, dev));
+  if (int e = current_cus(&cu_count)) return e;
   if (cu_count <= 0) return (int)hipErrorInvalidDevice;
 
   // the expectation comes from the host: a unit that computes wrongly must not produce its own
@@ -316,7 +315,7 @@ int gm_probe_cuscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed,
     GM_CHECK(hipEventRecord(ev.e1, nullptr));
     GM_CHECK(hipMemcpy(&distinct, &tab->distinct, sizeof(distinct), hipMemcpyDeviceToHost));
     float ms = 0;
-    GM_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if (int e = elapsed_ms(ev.e0, ev.e1, &ms)) return e;
     ms_sum += ms;
     ++rounds;
     if (rounds >= min_rounds && distinct >= (uint32_t)cu_count) break;
@@ -357,7 +356,7 @@ int gm_probe_cuscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed,
   if (n_cus) *n_cus = n;
   out->complete = out->cus_seen == out->cus_expected;
   out->kernel_ms = ms_sum;
-  out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  out->seconds = now_s() - t0;
   return 0;
 }
 

@@ -2,7 +2,6 @@
 // and the bit-exact burn-in loop. Part of libgm_probe.so (built with gm_probe.hip).
 // Measurements: profiles/history/r1_gemm/ (round 1 also timed eight other schedules, V0 V2-V4 V6-V9;
 // none beat V5, and they were removed: the GEMM is a burn-in load, not a product kernel).
-#include <chrono>
 
 #include "gm_probe.h"
 #include "gm_probe_common.h"
@@ -333,7 +332,7 @@ int gm_probe_gemm_nt_tflops(int dev, int M, int N, int K, int iters, double* tfl
   if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
   if (!e) e = (int)hipEventSynchronize(ev.e1);
   float ms = 0;
-  if (!e) e = (int)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+  if (!e) e = elapsed_ms(ev.e0, ev.e1, &ms);
   if (!e && ms > 0) *tflops = 2.0 * M * N * (double)K * iters / (ms * 1e-3) / 1e12;
   return e;
 }
@@ -407,7 +406,7 @@ int gm_probe_burn_in_flip(int dev, int n, double seconds, int n_flips,
   Events ev;
   GM_CHECK(ev.create());
   GM_CHECK(hipEventRecord(ev.e0, nullptr));
-  const auto t0 = std::chrono::steady_clock::now();
+  const double t0 = now_s();
   const size_t vec = elems / 8;  // 16-B compares
   int done = 0;
   // Batches of 8 GEMMs, each result compared bit-for-bit with the first one: the kernel is
@@ -419,13 +418,13 @@ int gm_probe_burn_in_flip(int dev, int n, double seconds, int n_flips,
       ++done;
     }
     if (!e) e = (int)hipDeviceSynchronize();
-    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const double el = now_s() - t0;
     if (el >= seconds) break;
   }
   if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
   if (!e) e = (int)hipEventSynchronize(ev.e1);
   float ms = 0;
-  if (!e) e = (int)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+  if (!e) e = elapsed_ms(ev.e0, ev.e1, &ms);
   unsigned long long bad = 0;
   if (!e) e = (int)hipMemcpy(&bad, dcount.p, sizeof(bad), hipMemcpyDeviceToHost);
   if (e) return e;

@@ -1,194 +1,54 @@
 // gm_hostlink.hip — host-link (PCIe) data and bandwidth test for gfx950: do bytes arrive intact
 // between pinned host memory and the GPU, and how fast?
 //
-// Three kernels from one template walk pinned host memory through its device mapping:
-//   k_hl_read   reads and checks every 64-bit word against the memtest pattern
-//   k_hl_write  writes the pattern
-//   k_hl_copy   reads one host buffer, checks it, writes what it read to a second host buffer
+// Three kinds of launch of the pattern-stream kernel (gm_pattern_stream.h) walk pinned host
+// memory through its device mapping:
+//   kread   reads and checks every 64-bit word against the memtest pattern
+//   kwrite  writes the pattern
+//   kcopy   reads one host buffer, checks it, writes what it read to a second host buffer
 // The link is narrow and latency-bound next to HBM, so the geometry is not memtest's: a caller-
 // chosen number of 256-thread blocks (a few tens fill the link and leave the other CUs alone),
-// a contiguous chunk per block in whole steps of U × 256 16-byte elements, all U loads of a lane
-// issued before the first is used, a 16-byte tail loop, nontemporal accesses. Lane l of a wave
-// touches base + 16 l: one wave-instruction is 1 KiB of contiguous host memory.
-//
-// The error path is memtest's: one OR per word on clean data, a cold report() otherwise.
+// U of 4 or 8, nontemporal accesses. Lane l of a wave touches base + 16 l: one wave-instruction
+// is 1 KiB of contiguous host memory.
 // The driver (gm_probe_hostlink) adds the copy-engine legs and the timing.
-#include "gm_probe.h"
-
-#include <hip/hip_runtime.h>
-#include <string.h>
-
 #include <atomic>
-#include <chrono>
 
 #include "gm_hostlink_host.h"
-#include "gm_memtest_pattern.h"
-#include "gm_probe_common.h"
+#include "gm_pattern_stream.h"
 
 namespace {
 
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-enum { kRead = 0, kWrite = 1, kCopy = 2 };
 constexpr int kDefaultUnroll = 8;
 constexpr int kDefaultBlocks = 16;
 
-struct DevResult {
-  unsigned long long words, bits, stuck;
-  unsigned int claims, pad;
-  gm_memtest_record_t rec[GM_MEMTEST_MAX_RECORDS];
-};
-
-struct Args {
-  uint64_t base;  // global byte offset of buf[0]
-  uint64_t seed;
-  uint64_t inv;   // 0 or ~0: XORed into the pattern value
-  uint64_t flip_offset, flip_mask;  // writers: word at global offset flip_offset ^= flip_mask
-  uint32_t pass;
-};
-
-template <uint32_t P>
-__device__ __forceinline__ uint64_t expect(const Args& a, uint64_t o) {
-  return gm_memtest_expected(P, a.seed, a.pass, o) ^ a.inv;
-}
-
-// Cold: entered per mismatching word only.
-__device__ __noinline__ void report(DevResult* res, uint64_t o, uint64_t e, uint64_t g,
-                                    uint32_t pattern, uint32_t pass) {
-  const uint64_t x = e ^ g;
-  atomicAdd(&res->words, 1ull);
-  atomicAdd(&res->bits, (unsigned long long)__popcll(x));
-  atomicOr(&res->stuck, (unsigned long long)x);
-  const unsigned int slot = atomicAdd(&res->claims, 1u);
-  if (slot < GM_MEMTEST_MAX_RECORDS) {
-    gm_memtest_record_t* r = &res->rec[slot];
-    r->offset = o;
-    r->expected = e;
-    r->got = g;
-    r->pattern = pattern;
-    r->pass = pass;
-  }
-}
-
-template <uint32_t P>
-__device__ __forceinline__ void check_pair(DevResult* res, const Args& a, uint64_t o, u64x2 got) {
-  const uint64_t e0 = expect<P>(a, o), e1 = expect<P>(a, o + 8);
-  if (got.x != e0) report(res, o, e0, got.x, P, a.pass);
-  if (got.y != e1) report(res, o + 8, e1, got.y, P, a.pass);
-}
-
-// The negative control: v is the element at global byte offset o.
-__device__ __forceinline__ u64x2 flipped(const Args& a, uint64_t o, u64x2 v) {
-  v.x ^= o == a.flip_offset ? a.flip_mask : 0;
-  v.y ^= o + 8 == a.flip_offset ? a.flip_mask : 0;
-  return v;
-}
-
-// n and per_block count 16-byte elements; src is read (kRead, kCopy), dst written (kWrite, kCopy).
-template <uint32_t P, int kMode, int U>
-__global__ __launch_bounds__(256) void k_hl(const u64x2* __restrict__ src, u64x2* __restrict__ dst,
-                                            size_t n, size_t per_block, Args a, DevResult* res) {
-  const size_t begin = (size_t)blockIdx.x * per_block;
-  if (begin >= n) return;
-  const size_t end = per_block < n - begin ? begin + per_block : n;
-  size_t i = begin + threadIdx.x;
-  for (; i + (size_t)(U - 1) * 256 < end; i += (size_t)U * 256) {
-    if constexpr (kMode == kWrite) {
-#pragma unroll
-      for (int c = 0; c < U; ++c) {
-        const uint64_t o = a.base + (uint64_t)(i + c * 256) * 16;
-        const u64x2 v = {expect<P>(a, o), expect<P>(a, o + 8)};
-        __builtin_nontemporal_store(flipped(a, o, v), &dst[i + c * 256]);
-      }
-    } else {
-      u64x2 r[U];
-#pragma unroll
-      for (int c = 0; c < U; ++c) r[c] = __builtin_nontemporal_load(&src[i + c * 256]);
-      uint64_t flag = 0;
-#pragma unroll
-      for (int c = 0; c < U; ++c) {
-        const uint64_t o = a.base + (uint64_t)(i + c * 256) * 16;
-        flag |= (r[c].x ^ expect<P>(a, o)) | (r[c].y ^ expect<P>(a, o + 8));
-        if constexpr (kMode == kCopy)
-          __builtin_nontemporal_store(flipped(a, o, r[c]), &dst[i + c * 256]);
-      }
-      if (flag != 0) {
-#pragma unroll  // constant indices keep r[] in registers
-        for (int c = 0; c < U; ++c)
-          check_pair<P>(res, a, a.base + (uint64_t)(i + c * 256) * 16, r[c]);
-      }
-    }
-  }
-  for (; i < end; i += 256) {
-    const uint64_t o = a.base + (uint64_t)i * 16;
-    const uint64_t e0 = expect<P>(a, o), e1 = expect<P>(a, o + 8);
-    if constexpr (kMode == kWrite) {
-      const u64x2 v = {e0, e1};
-      __builtin_nontemporal_store(flipped(a, o, v), &dst[i]);
-    } else {
-      const u64x2 g = __builtin_nontemporal_load(&src[i]);
-      if constexpr (kMode == kCopy) __builtin_nontemporal_store(flipped(a, o, g), &dst[i]);
-      if (((g.x ^ e0) | (g.y ^ e1)) != 0) check_pair<P>(res, a, o, g);
-    }
-  }
-}
-
 std::atomic<int> g_unroll{kDefaultUnroll};
 
-template <uint32_t P, int U>
-void launch_pu(int mode, unsigned int blocks, hipStream_t s, const u64x2* src, u64x2* dst,
-               size_t n, size_t per_block, const Args& a, DevResult* res) {
-  const dim3 grid(blocks), block(256);
-  if (mode == kRead)
-    hipLaunchKernelGGL((k_hl<P, kRead, U>), grid, block, 0, s, src, dst, n, per_block, a, res);
-  else if (mode == kWrite)
-    hipLaunchKernelGGL((k_hl<P, kWrite, U>), grid, block, 0, s, src, dst, n, per_block, a, res);
-  else
-    hipLaunchKernelGGL((k_hl<P, kCopy, U>), grid, block, 0, s, src, dst, n, per_block, a, res);
-}
-
-template <uint32_t P>
-void launch_p(int u, int mode, unsigned int blocks, hipStream_t s, const u64x2* src, u64x2* dst,
-              size_t n, size_t per_block, const Args& a, DevResult* res) {
-  if (u == 4)
-    launch_pu<P, 4>(mode, blocks, s, src, dst, n, per_block, a, res);
-  else
-    launch_pu<P, 8>(mode, blocks, s, src, dst, n, per_block, a, res);
-}
-
-// src and dst are device addresses of `bytes` each (whichever the mode uses).
-int launch(int mode, uint32_t pattern, int blocks, hipStream_t s, const void* src, void* dst,
+// `from` (kCheck, kCopy) and `to` (kWrite, kCopy) are device addresses of `bytes` each.
+// Nontemporal stores, the negative control compiled in, U from gm_probe_hostlink_unroll.
+int launch(int mode, uint32_t pattern, int blocks, hipStream_t s, const void* from, void* to,
            uint64_t bytes, const Args& a, DevResult* res) {
   const int u = g_unroll.load();
-  const size_t n = bytes / 16, step = (size_t)u * 256;
-  const size_t nb = (size_t)blocks;
-  const size_t per_block = ((n + nb - 1) / nb + step - 1) / step * step;
-  const u64x2* sp = (const u64x2*)src;
-  u64x2* dp = (u64x2*)dst;
-  const unsigned int g = (unsigned int)blocks;
-  switch (pattern) {
-    case GM_MEMTEST_ADDR: launch_p<GM_MEMTEST_ADDR>(u, mode, g, s, sp, dp, n, per_block, a, res); break;
-    case GM_MEMTEST_SOLID: launch_p<GM_MEMTEST_SOLID>(u, mode, g, s, sp, dp, n, per_block, a, res); break;
-    case GM_MEMTEST_CHECKER: launch_p<GM_MEMTEST_CHECKER>(u, mode, g, s, sp, dp, n, per_block, a, res); break;
-    case GM_MEMTEST_WALK: launch_p<GM_MEMTEST_WALK>(u, mode, g, s, sp, dp, n, per_block, a, res); break;
-    case GM_MEMTEST_RANDOM: launch_p<GM_MEMTEST_RANDOM>(u, mode, g, s, sp, dp, n, per_block, a, res); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
-}
-
-bool one_pattern(uint32_t p) {
-  return p == GM_MEMTEST_ADDR || p == GM_MEMTEST_SOLID || p == GM_MEMTEST_CHECKER ||
-         p == GM_MEMTEST_WALK || p == GM_MEMTEST_RANDOM;
+  const size_t n = bytes / 16;
+  const StreamLaunch l{gm_pattern_chunks(n, (size_t)blocks, (size_t)u * 256), s,
+                       mode == kCheck ? const_cast<void*>(from) : to, from, n, a, res};
+  const bool known = dispatch_pattern(pattern, [&](auto p) {
+    constexpr uint32_t P = decltype(p)::value;
+    if (mode == kCheck)
+      u == 4 ? l.run<P, kCheck, 4, true, true>() : l.run<P, kCheck, 8, true, true>();
+    else if (mode == kWrite)
+      u == 4 ? l.run<P, kWrite, 4, true, true>() : l.run<P, kWrite, 8, true, true>();
+    else
+      u == 4 ? l.run<P, kCopy, 4, true, true>() : l.run<P, kCopy, 8, true, true>();
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 bool one_leg(uint32_t l) { return l != 0 && (l & (l - 1)) == 0 && (l & ~(uint32_t)GM_HOSTLINK_ALL) == 0; }
 
 bool buffer_ok(const void* ptr, uint64_t bytes, uint32_t pattern, uint64_t base_offset,
                int blocks) {
-  return ptr != nullptr && ((uintptr_t)ptr & 15) == 0 && bytes != 0 && (bytes & 15) == 0 &&
-         (uintptr_t)ptr + bytes >= (uintptr_t)ptr && (base_offset & 7) == 0 &&
-         one_pattern(pattern) && blocks >= 1 && blocks <= GM_HOSTLINK_MAX_BLOCKS;
+  return buffer_ok(ptr, bytes, pattern, base_offset) && (uintptr_t)ptr + bytes >= (uintptr_t)ptr &&
+         blocks >= 1 && blocks <= GM_HOSTLINK_MAX_BLOCKS;
 }
 
 // Device address of pinned host memory [host, host + bytes); an error for anything else.
@@ -209,58 +69,7 @@ int device_view(const void* host, uint64_t bytes, void** dev) {
   return *dev ? 0 : (int)hipErrorInvalidValue;
 }
 
-void export_errors(const DevResult& h, gm_memtest_result_t* out) {
-  out->words_in_error = h.words;
-  out->bit_errors = h.bits;
-  out->stuck_mask = h.stuck;
-  out->records_filled = h.claims < GM_MEMTEST_MAX_RECORDS ? h.claims : GM_MEMTEST_MAX_RECORDS;
-  for (uint32_t i = 0; i < out->records_filled; ++i) out->records[i] = h.rec[i];
-}
-
-// One verifying launch on caller-owned memory, waited for.
-int checked_launch(int mode, uint32_t pattern, int blocks, hipStream_t s, const void* src,
-                   void* dst, uint64_t bytes, const Args& a, gm_memtest_result_t* out) {
-  DevBuf dres;
-  GM_CHECK(dres.alloc(sizeof(DevResult)));
-  GM_CHECK(hipMemsetAsync(dres.p, 0, sizeof(DevResult), s));
-  if (int e = launch(mode, pattern, blocks, s, src, dst, bytes, a, (DevResult*)dres.p)) return e;
-  DevResult h;
-  GM_CHECK(hipMemcpyAsync(&h, dres.p, sizeof(h), hipMemcpyDeviceToHost, s));
-  GM_CHECK(hipStreamSynchronize(s));
-  out->bytes_tested = bytes;
-  export_errors(h, out);
-  return 0;
-}
-
-struct PinnedBuf {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) {
-    return hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
-  }
-  ~PinnedBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-};
-struct Stream {
-  hipStream_t s = nullptr;
-  hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
-  ~Stream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-struct Event {
-  hipEvent_t e = nullptr;
-  hipError_t create() { return hipEventCreate(&e); }
-  ~Event() {
-    if (e) (void)hipEventDestroy(e);
-  }
-};
-
 const char* const kLegNames[GM_HOSTLINK_LEGS] = {"h2d", "d2h", "bidir", "kread", "kwrite", "kduplex"};
-
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // Everything one call of the driver holds.
 struct Run {
@@ -351,14 +160,7 @@ struct Run {
     host_s += now_s() - t;
   }
   void flip_host_source() { ((uint64_t*)ha.p)[flip_offset / 8] ^= flip_mask; }
-  int flip_device_source() {
-    char* at = (char*)da.p + flip_offset;
-    uint64_t word = 0;
-    GM_CHECK(hipMemcpy(&word, at, 8, hipMemcpyDeviceToHost));
-    word ^= flip_mask;
-    GM_CHECK(hipMemcpy(at, &word, 8, hipMemcpyHostToDevice));
-    return 0;
-  }
+  int flip_device_source() { return xor_device_word((char*)da.p + flip_offset, flip_mask); }
   // db = ~P, da = P (device side, as the HBM test does it)
   int device_poison(uint32_t pattern, uint32_t pass) {
     if (int e = gm_probe_memtest_fill(db.p, bytes, pattern, 1, seed, pass, 0, s1.s)) return e;
@@ -380,13 +182,13 @@ struct Run {
     GM_CHECK(hipEventRecord(end1.e, s1.s));
     GM_CHECK(hipEventSynchronize(end1.e));
     float ms = 0;
-    GM_CHECK(hipEventElapsedTime(&ms, start.e, end1.e));
+    if (int e = elapsed_ms(start.e, end1.e, &ms)) return e;
     add_time(l, moved_per_iter * (uint64_t)iters, ms);
     return 0;
   }
 
   Args args(uint32_t pass, bool flip) const {
-    return Args{0, seed, 0, flip ? flip_offset : 0, flip ? flip_mask : 0, pass};
+    return Args{0, seed, 0, pass, flip ? flip_offset : 0, flip ? flip_mask : 0};
   }
   // the result of the last timed launch (k == iters - 1) is the one that counts
   DevResult* result_for(int k) const {
@@ -440,8 +242,8 @@ struct Run {
       GM_CHECK(hipEventSynchronize(end1.e));
       GM_CHECK(hipEventSynchronize(end2.e));
       float m1 = 0, m2 = 0;
-      GM_CHECK(hipEventElapsedTime(&m1, start.e, end1.e));
-      GM_CHECK(hipEventElapsedTime(&m2, start.e, end2.e));
+      if (int e = elapsed_ms(start.e, end1.e, &m1)) return e;
+      if (int e = elapsed_ms(start.e, end2.e, &m2)) return e;
       const uint64_t moved = bytes * (uint64_t)iters;
       add_time(&out->bidir_h2d, moved, m1);
       add_time(&out->bidir_d2h, moved, m2);
@@ -461,8 +263,8 @@ struct Run {
   }
   int leg_kernel(uint32_t leg, int idx, int mode, uint32_t pattern, uint32_t pass) {
     const bool f = flips(leg);
-    const bool reads = mode != kWrite, writes = mode != kRead;
-    if (f && mode == kRead) flip_host_source();
+    const bool reads = mode != kWrite, writes = mode != kCheck;
+    if (f && mode == kCheck) flip_host_source();
     if (writes) host_poison();
     int e = 0;
     if (reads) {
@@ -475,7 +277,7 @@ struct Run {
         return launch(mode, pattern, blocks, s1.s, ha_dev, hb_dev, bytes, a, result_for(k));
       });
     if (e) (void)hipStreamSynchronize(s1.s);
-    if (f && mode == kRead) flip_host_source();
+    if (f && mode == kCheck) flip_host_source();
     if (e) return e;
     if (reads)
       if (int e2 = kernel_check(leg, s1.s)) return e2;
@@ -512,7 +314,7 @@ int gm_probe_hostlink_kwrite(void* host_ptr, uint64_t bytes, uint32_t pattern, i
     return (int)hipErrorInvalidValue;
   void* dev = nullptr;
   if (int e = device_view(host_ptr, bytes, &dev)) return e;
-  const Args a{base_offset, seed, invert ? ~0ull : 0ull, flip_offset, flip_mask, pass};
+  const Args a{base_offset, seed, invert ? ~0ull : 0ull, pass, flip_offset, flip_mask};
   return launch(kWrite, pattern, blocks, (hipStream_t)stream, nullptr, dev, bytes, a, nullptr);
 }
 
@@ -524,8 +326,11 @@ int gm_probe_hostlink_kread(const void* host_ptr, uint64_t bytes, uint32_t patte
   if (!buffer_ok(host_ptr, bytes, pattern, base_offset, blocks)) return (int)hipErrorInvalidValue;
   void* dev = nullptr;
   if (int e = device_view(host_ptr, bytes, &dev)) return e;
-  const Args a{base_offset, seed, invert ? ~0ull : 0ull, 0, 0, pass};
-  return checked_launch(kRead, pattern, blocks, (hipStream_t)stream, dev, nullptr, bytes, a, out);
+  const Args a{base_offset, seed, invert ? ~0ull : 0ull, pass};
+  hipStream_t s = (hipStream_t)stream;
+  return checked_launch(s, bytes, out, [&](DevResult* res) {
+    return launch(kCheck, pattern, blocks, s, dev, nullptr, bytes, a, res);
+  });
 }
 
 int gm_probe_hostlink_kcopy(const void* src_host, void* dst_host, uint64_t bytes, uint32_t pattern,
@@ -537,13 +342,16 @@ int gm_probe_hostlink_kcopy(const void* src_host, void* dst_host, uint64_t bytes
   if (!buffer_ok(src_host, bytes, pattern, base_offset, blocks) ||
       !buffer_ok(dst_host, bytes, pattern, base_offset, blocks) || (flip_offset & 7))
     return (int)hipErrorInvalidValue;
-  const uintptr_t s = (uintptr_t)src_host, d = (uintptr_t)dst_host;
-  if (s < d + bytes && d < s + bytes) return (int)hipErrorInvalidValue;
+  const uintptr_t sa = (uintptr_t)src_host, da = (uintptr_t)dst_host;
+  if (sa < da + bytes && da < sa + bytes) return (int)hipErrorInvalidValue;
   void *sdev = nullptr, *ddev = nullptr;
   if (int e = device_view(src_host, bytes, &sdev)) return e;
   if (int e = device_view(dst_host, bytes, &ddev)) return e;
-  const Args a{base_offset, seed, invert ? ~0ull : 0ull, flip_offset, flip_mask, pass};
-  return checked_launch(kCopy, pattern, blocks, (hipStream_t)stream, sdev, ddev, bytes, a, out);
+  const Args a{base_offset, seed, invert ? ~0ull : 0ull, pass, flip_offset, flip_mask};
+  hipStream_t s = (hipStream_t)stream;
+  return checked_launch(s, bytes, out, [&](DevResult* res) {
+    return launch(kCopy, pattern, blocks, s, sdev, ddev, bytes, a, res);
+  });
 }
 
 int gm_probe_hostlink(int dev, uint64_t bytes, uint32_t legs_mask, uint32_t pattern_mask,
@@ -616,7 +424,7 @@ int gm_probe_hostlink(int dev, uint64_t bytes, uint32_t legs_mask, uint32_t patt
           case GM_HOSTLINK_H2D: e = r.leg_h2d(pattern, ps); break;
           case GM_HOSTLINK_D2H: e = r.leg_d2h(pattern, ps); break;
           case GM_HOSTLINK_BIDIR: e = r.leg_bidir(pattern, ps); break;
-          case GM_HOSTLINK_KREAD: e = r.leg_kernel(leg, idx, kRead, pattern, ps); break;
+          case GM_HOSTLINK_KREAD: e = r.leg_kernel(leg, idx, kCheck, pattern, ps); break;
           case GM_HOSTLINK_KWRITE: e = r.leg_kernel(leg, idx, kWrite, pattern, ps); break;
           default: e = r.leg_kernel(leg, idx, kCopy, pattern, ps); break;
         }

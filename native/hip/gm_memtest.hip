@@ -1,239 +1,45 @@
 // gm_memtest.hip — HBM pattern test for gfx950: does the VRAM hold what is written to it?
 //
-// Three bandwidth-bound kernels from one template, in the form of k_read_chunk / k_copy_chunk
-// (gm_probe.hip): a contiguous chunk per 256-thread block, 16 B per lane per access, 8 nontemporal
-// loads in flight per lane before the compares, a 16-byte tail loop, CUs × 2 blocks.
+// Three kinds of launch of the pattern-stream kernel (gm_pattern_stream.h), 8 loads in flight per
+// lane, CUs × 2 blocks:
 //   fill           writes P (or ~P)
 //   verify_invert  reads and checks P, writes ~P over the same words
 //   verify         reads and checks
-// The expected value of a word is a pure function of its global byte offset in the test region
-// (gm_memtest_pattern.h), so nothing but the buffer itself is read. All three walk the region in
-// the same order: what was written first is read first, after everything else has gone through
-// the caches. Inside one launch the blocks run in whatever order the dispatcher picks; there is
-// no ascending or descending direction as in a CPU march test.
-//
-// The error path costs one OR per word on clean memory: each lane ORs expected ^ got of its 16
-// words into one flag and only a lane whose flag is nonzero looks at the words again.
-#include "gm_probe.h"
-
-#include <hip/hip_runtime.h>
-#include <string.h>
-
+// All three walk the region in the same order: what was written first is read first, after
+// everything else has gone through the caches. Inside one launch the blocks run in whatever
+// order the dispatcher picks; there is no ascending or descending direction as in a CPU march
+// test.
 #include <atomic>
-#include <chrono>
 #include <deque>
 
-#include "gm_memtest_pattern.h"
-#include "gm_probe_common.h"
+#include "gm_pattern_stream.h"
 
 namespace {
 
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-enum { kFill = 0, kVerify = 1, kVerifyInvert = 2 };
 constexpr int kInFlight = 8;          // 16-B accesses per lane per unrolled step
 constexpr int kBlocksPerCu = 2;       // gm_probe_hbm_read's default geometry
 constexpr size_t kStepElems = (size_t)kInFlight * 256;  // 16-B elements per block per step
 
-struct DevResult {
-  unsigned long long words, bits, stuck;
-  unsigned int claims, pad;
-  gm_memtest_record_t rec[GM_MEMTEST_MAX_RECORDS];
-};
-
-struct Args {
-  uint64_t base;  // global byte offset of buf[0] in the region
-  uint64_t seed;
-  uint64_t inv;   // 0 or ~0: XORed into the pattern value
-  uint32_t pass;
-};
-
-template <uint32_t P>
-__device__ __forceinline__ uint64_t expect(const Args& a, uint64_t o) {
-  return gm_memtest_expected(P, a.seed, a.pass, o) ^ a.inv;
-}
-
-// Cold: entered per mismatching word only.
-__device__ __noinline__ void report(DevResult* res, uint64_t o, uint64_t e, uint64_t g,
-                                    uint32_t pattern, uint32_t pass) {
-  const uint64_t x = e ^ g;
-  atomicAdd(&res->bits, (unsigned long long)__popcll(x));
-  atomicOr(&res->stuck, (unsigned long long)x);
-  const unsigned int slot = atomicAdd(&res->claims, 1u);
-  if (slot < GM_MEMTEST_MAX_RECORDS) {
-    gm_memtest_record_t* r = &res->rec[slot];
-    r->offset = o;
-    r->expected = e;
-    r->got = g;
-    r->pattern = pattern;
-    r->pass = pass;
-  }
-}
-
-template <uint32_t P>
-__device__ __forceinline__ uint32_t check_pair(DevResult* res, const Args& a, uint64_t o,
-                                               u64x2 got) {
-  uint32_t bad = 0;
-  const uint64_t e0 = expect<P>(a, o), e1 = expect<P>(a, o + 8);
-  if (got.x != e0) {
-    report(res, o, e0, got.x, P, a.pass);
-    ++bad;
-  }
-  if (got.y != e1) {
-    report(res, o + 8, e1, got.y, P, a.pass);
-    ++bad;
-  }
-  return bad;
-}
-
-template <bool kNt>
-__device__ __forceinline__ void put(u64x2* p, u64x2 v) {
-  if constexpr (kNt)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
-}
-
-// n and per_block count 16-byte elements.
-template <uint32_t P, int kMode, bool kNtStore>
-__global__ __launch_bounds__(256) void k_memtest(u64x2* __restrict__ buf, size_t n,
-                                                 size_t per_block, Args a, DevResult* res) {
-  const size_t begin = (size_t)blockIdx.x * per_block;
-  const size_t end = begin + per_block < n ? begin + per_block : n;
-  uint32_t bad = 0;
-  size_t i = begin + threadIdx.x;
-  for (; i + (kInFlight - 1) * 256 < end; i += kStepElems) {
-    if constexpr (kMode == kFill) {
-#pragma unroll
-      for (int c = 0; c < kInFlight; ++c) {
-        const uint64_t o = a.base + (uint64_t)(i + c * 256) * 16;
-        const u64x2 v = {expect<P>(a, o), expect<P>(a, o + 8)};
-        put<kNtStore>(&buf[i + c * 256], v);
-      }
-    } else {
-      u64x2 r[kInFlight];
-#pragma unroll
-      for (int c = 0; c < kInFlight; ++c) r[c] = __builtin_nontemporal_load(&buf[i + c * 256]);
-      uint64_t flag = 0;
-#pragma unroll
-      for (int c = 0; c < kInFlight; ++c) {
-        const uint64_t o = a.base + (uint64_t)(i + c * 256) * 16;
-        const uint64_t e0 = expect<P>(a, o), e1 = expect<P>(a, o + 8);
-        flag |= (r[c].x ^ e0) | (r[c].y ^ e1);
-        if constexpr (kMode == kVerifyInvert) {
-          const u64x2 v = {~e0, ~e1};
-          put<kNtStore>(&buf[i + c * 256], v);
-        }
-      }
-      if (flag != 0) {
-#pragma unroll  // constant indices keep r[] in registers
-        for (int c = 0; c < kInFlight; ++c)
-          bad += check_pair<P>(res, a, a.base + (uint64_t)(i + c * 256) * 16, r[c]);
-      }
-    }
-  }
-  for (; i < end; i += 256) {
-    const uint64_t o = a.base + (uint64_t)i * 16;
-    const uint64_t e0 = expect<P>(a, o), e1 = expect<P>(a, o + 8);
-    if constexpr (kMode == kFill) {
-      const u64x2 v = {e0, e1};
-      buf[i] = v;
-    } else {
-      const u64x2 g = buf[i];
-      if constexpr (kMode == kVerifyInvert) {
-        const u64x2 v = {~e0, ~e1};
-        buf[i] = v;
-      }
-      if (((g.x ^ e0) | (g.y ^ e1)) != 0) bad += check_pair<P>(res, a, o, g);
-    }
-  }
-  if constexpr (kMode != kFill) {
-    // one atomic per wave, and only from a wave that saw a mismatch (as k_count_diff does)
-    unsigned long long local = bad;
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, kWave);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(&res->words, local);
-  }
-}
-
 std::atomic<int> g_nt_store{1};
 
-struct Geometry {
-  unsigned int grid;
-  size_t per_block;
-};
-
-// CUs × kBlocksPerCu blocks, each a whole number of unrolled steps; blocks whose chunk would
-// start past the end are not launched.
-Geometry geometry(size_t n, int cus) {
-  const size_t blocks = (size_t)(cus > 0 ? cus : 1) * kBlocksPerCu;
-  const size_t per_block = ((n + blocks - 1) / blocks + kStepElems - 1) / kStepElems * kStepElems;
-  return {(unsigned int)((n + per_block - 1) / per_block), per_block};
-}
-
-template <uint32_t P>
-void launch_p(int mode, bool nt, const Geometry& g, hipStream_t s, u64x2* buf, size_t n,
-              const Args& a, DevResult* res) {
-  const dim3 grid(g.grid), block(256);
-  if (mode == kFill) {
-    if (nt)
-      hipLaunchKernelGGL((k_memtest<P, kFill, true>), grid, block, 0, s, buf, n, g.per_block, a,
-                         res);
-    else
-      hipLaunchKernelGGL((k_memtest<P, kFill, false>), grid, block, 0, s, buf, n, g.per_block, a,
-                         res);
-  } else if (mode == kVerifyInvert) {
-    if (nt)
-      hipLaunchKernelGGL((k_memtest<P, kVerifyInvert, true>), grid, block, 0, s, buf, n,
-                         g.per_block, a, res);
-    else
-      hipLaunchKernelGGL((k_memtest<P, kVerifyInvert, false>), grid, block, 0, s, buf, n,
-                         g.per_block, a, res);
-  } else {
-    hipLaunchKernelGGL((k_memtest<P, kVerify, false>), grid, block, 0, s, buf, n, g.per_block, a,
-                       res);
-  }
-}
-
+// The store variant picks the writing kernels; verify stores nothing and has one.
 int launch(int mode, uint32_t pattern, int cus, hipStream_t s, void* ptr, uint64_t bytes,
            const Args& a, DevResult* res) {
   const size_t n = bytes / 16;
-  const Geometry g = geometry(n, cus);
+  const size_t blocks = (size_t)(cus > 0 ? cus : 1) * kBlocksPerCu;
+  const StreamLaunch l{gm_pattern_chunks(n, blocks, kStepElems), s, ptr, nullptr, n, a, res};
   const bool nt = g_nt_store.load() != 0;
-  u64x2* buf = (u64x2*)ptr;
-  switch (pattern) {
-    case GM_MEMTEST_ADDR: launch_p<GM_MEMTEST_ADDR>(mode, nt, g, s, buf, n, a, res); break;
-    case GM_MEMTEST_SOLID: launch_p<GM_MEMTEST_SOLID>(mode, nt, g, s, buf, n, a, res); break;
-    case GM_MEMTEST_CHECKER: launch_p<GM_MEMTEST_CHECKER>(mode, nt, g, s, buf, n, a, res); break;
-    case GM_MEMTEST_WALK: launch_p<GM_MEMTEST_WALK>(mode, nt, g, s, buf, n, a, res); break;
-    case GM_MEMTEST_RANDOM: launch_p<GM_MEMTEST_RANDOM>(mode, nt, g, s, buf, n, a, res); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
-}
-
-bool one_pattern(uint32_t p) {
-  return p == GM_MEMTEST_ADDR || p == GM_MEMTEST_SOLID || p == GM_MEMTEST_CHECKER ||
-         p == GM_MEMTEST_WALK || p == GM_MEMTEST_RANDOM;
-}
-
-bool buffer_ok(const void* ptr, uint64_t bytes, uint32_t pattern, uint64_t base_offset) {
-  return ptr != nullptr && ((uintptr_t)ptr & 15) == 0 && bytes != 0 && (bytes & 15) == 0 &&
-         (base_offset & 7) == 0 && one_pattern(pattern);
-}
-
-int current_cus(int* cus) {
-  int dev = 0;
-  GM_CHECK(hipGetDevice(&dev));
-  GM_CHECK(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
-  return 0;
-}
-
-void export_errors(const DevResult& h, gm_memtest_result_t* out) {
-  out->words_in_error = h.words;
-  out->bit_errors = h.bits;
-  out->stuck_mask = h.stuck;
-  out->records_filled = h.claims < GM_MEMTEST_MAX_RECORDS ? h.claims : GM_MEMTEST_MAX_RECORDS;
-  for (uint32_t i = 0; i < out->records_filled; ++i) out->records[i] = h.rec[i];
+  const bool known = dispatch_pattern(pattern, [&](auto p) {
+    constexpr uint32_t P = decltype(p)::value;
+    if (mode == kCheck)
+      l.run<P, kCheck, kInFlight, false, false>();
+    else if (mode == kWrite)
+      nt ? l.run<P, kWrite, kInFlight, true, false>() : l.run<P, kWrite, kInFlight, false, false>();
+    else
+      nt ? l.run<P, kCheckInvert, kInFlight, true, false>()
+         : l.run<P, kCheckInvert, kInFlight, false, false>();
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 struct Piece {
@@ -276,7 +82,7 @@ int gm_probe_memtest_fill(void* ptr, uint64_t bytes, uint32_t pattern, int inver
   int cus = 0;
   if (int e = current_cus(&cus)) return e;
   const Args a{base_offset, seed, invert ? ~0ull : 0ull, pass};
-  return launch(kFill, pattern, cus, (hipStream_t)stream, ptr, bytes, a, nullptr);
+  return launch(kWrite, pattern, cus, (hipStream_t)stream, ptr, bytes, a, nullptr);
 }
 
 int gm_probe_memtest_verify(void* ptr, uint64_t bytes, uint32_t pattern, int invert,
@@ -288,19 +94,10 @@ int gm_probe_memtest_verify(void* ptr, uint64_t bytes, uint32_t pattern, int inv
   int cus = 0;
   if (int e = current_cus(&cus)) return e;
   hipStream_t s = (hipStream_t)stream;
-  DevBuf dres;
-  GM_CHECK(dres.alloc(sizeof(DevResult)));
-  GM_CHECK(hipMemsetAsync(dres.p, 0, sizeof(DevResult), s));
   const Args a{base_offset, seed, invert ? ~0ull : 0ull, pass};
-  if (int e = launch(write_inverse ? kVerifyInvert : kVerify, pattern, cus, s, ptr, bytes, a,
-                     (DevResult*)dres.p))
-    return e;
-  DevResult h;
-  GM_CHECK(hipMemcpyAsync(&h, dres.p, sizeof(h), hipMemcpyDeviceToHost, s));
-  GM_CHECK(hipStreamSynchronize(s));
-  out->bytes_tested = bytes;
-  export_errors(h, out);
-  return 0;
+  return checked_launch(s, bytes, out, [&](DevResult* res) {
+    return launch(write_inverse ? kCheckInvert : kCheck, pattern, cus, s, ptr, bytes, a, res);
+  });
 }
 
 int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pattern_mask,
@@ -317,7 +114,7 @@ int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pat
   if (!g.ok) return (int)hipErrorInvalidDevice;
   int cus = 0;
   if (int e = current_cus(&cus)) return e;
-  const auto t0 = std::chrono::steady_clock::now();
+  const double t0 = now_s();
   if (chunk_bytes == 0) chunk_bytes = 8ull << 30;
 
   // the region: allocations of at most chunk_bytes, each with its global base offset
@@ -355,7 +152,7 @@ int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pat
   {
     // untimed first launch: the code object is loaded here, not between a timed pair of events
     const uint64_t warm = pieces[0].bytes < 65536 ? pieces[0].bytes : 65536;
-    if (int e = launch(kFill, GM_MEMTEST_SOLID, cus, nullptr, pieces[0].buf.p, warm,
+    if (int e = launch(kWrite, GM_MEMTEST_SOLID, cus, nullptr, pieces[0].buf.p, warm,
                        Args{0, seed, 0, 0}, nullptr))
       return e;
     GM_CHECK(hipStreamSynchronize(nullptr));
@@ -374,7 +171,7 @@ int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pat
     if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
     if (!e) e = (int)hipEventSynchronize(ev.e1);
     float ms = 0;
-    if (!e) e = (int)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+    if (!e) e = elapsed_ms(ev.e0, ev.e1, &ms);
     ms_kind[mode] += ms;
     ++launches_kind[mode];
     return e;
@@ -382,11 +179,7 @@ int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pat
   auto flip = [&]() -> int {
     for (Piece& p : pieces) {
       if (flip_offset < p.base || flip_offset + 8 > p.base + p.bytes) continue;
-      char* at = (char*)p.buf.p + (flip_offset - p.base);
-      uint64_t word = 0;
-      GM_CHECK(hipMemcpy(&word, at, 8, hipMemcpyDeviceToHost));
-      word ^= flip_mask;
-      GM_CHECK(hipMemcpy(at, &word, 8, hipMemcpyHostToDevice));
+      if (int e = xor_device_word((char*)p.buf.p + (flip_offset - p.base), flip_mask)) return e;
     }
     return 0;
   };
@@ -395,10 +188,10 @@ int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pat
   for (uint32_t pattern = 1; pattern <= GM_MEMTEST_RANDOM && !e; pattern <<= 1) {
     if (!(pattern_mask & pattern)) continue;
     for (int pass = 0; pass < passes && !e; ++pass) {
-      e = sweep(kFill, pattern, false, (uint32_t)pass);
+      e = sweep(kWrite, pattern, false, (uint32_t)pass);
       if (!e && flip_mask) e = flip();
-      if (!e) e = sweep(kVerifyInvert, pattern, false, (uint32_t)pass);
-      if (!e) e = sweep(kVerify, pattern, true, (uint32_t)pass);
+      if (!e) e = sweep(kCheckInvert, pattern, false, (uint32_t)pass);
+      if (!e) e = sweep(kCheck, pattern, true, (uint32_t)pass);
     }
   }
   if (e) return e;
@@ -408,13 +201,12 @@ int gm_probe_memtest(int dev, uint64_t bytes, uint64_t chunk_bytes, uint32_t pat
   out->bytes_tested = have;
   out->allocations = (uint32_t)pieces.size();
   const double b = (double)have;
-  if (ms_kind[kFill] > 0) out->write_gbps = b * launches_kind[kFill] / (ms_kind[kFill] * 1e-3) / 1e9;
-  if (ms_kind[kVerify] > 0)
-    out->read_gbps = b * launches_kind[kVerify] / (ms_kind[kVerify] * 1e-3) / 1e9;
-  if (ms_kind[kVerifyInvert] > 0)
-    out->rw_gbps = 2.0 * b * launches_kind[kVerifyInvert] / (ms_kind[kVerifyInvert] * 1e-3) / 1e9;
-  out->seconds =
-      std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (ms_kind[kWrite] > 0) out->write_gbps = b * launches_kind[kWrite] / (ms_kind[kWrite] * 1e-3) / 1e9;
+  if (ms_kind[kCheck] > 0)
+    out->read_gbps = b * launches_kind[kCheck] / (ms_kind[kCheck] * 1e-3) / 1e9;
+  if (ms_kind[kCheckInvert] > 0)
+    out->rw_gbps = 2.0 * b * launches_kind[kCheckInvert] / (ms_kind[kCheckInvert] * 1e-3) / 1e9;
+  out->seconds = now_s() - t0;
   return 0;
 }
 

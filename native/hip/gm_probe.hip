@@ -14,7 +14,6 @@
 #include <strings.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <mutex>
 #include <random>
@@ -337,13 +336,6 @@ int launch_read(const float4* src, uint32_t* sink, size_t n, int blocks, hipStre
 
 bool aligned16(const void* p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
 
-int current_cus(int* cus) {
-  int dev = 0;
-  GM_CHECK(hipGetDevice(&dev));
-  GM_CHECK(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
-  return 0;
-}
-
 uint16_t f2bf(float f) {
   uint32_t u;
   memcpy(&u, &f, 4);
@@ -400,12 +392,12 @@ int gm_probe_quick(int dev, int* ok, double* elapsed_us) {
   if (!g.ok) return (int)hipErrorInvalidDevice;
   Scratch* s = scratch(dev);
   if (!s) return (int)hipErrorOutOfMemory;
-  const auto t0 = std::chrono::steady_clock::now();
+  const double t0 = now_s();
   const uint32_t salt = 0x9e3779b9u ^ (uint32_t)dev;
   hipLaunchKernelGGL(k_quick, dim3(1), dim3(64), 0, 0, s->quick, salt);
   GM_CHECK(hipGetLastError());
   GM_CHECK(hipMemcpy(s->quick_host, s->quick, 66 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  const auto t1 = std::chrono::steady_clock::now();
+  const double t1 = now_s();
   uint32_t sum = 0;
   bool good = true;
   for (uint32_t l = 0; l < 64; ++l) {
@@ -415,7 +407,7 @@ int gm_probe_quick(int dev, int* ok, double* elapsed_us) {
   }
   good &= s->quick_host[64] == sum && s->quick_host[65] == 64;
   *ok = good ? 1 : 0;
-  *elapsed_us = std::chrono::duration<double, std::micro>(t1 - t0).count();
+  *elapsed_us = (t1 - t0) * 1e6;
   return 0;
 }
 
@@ -471,7 +463,7 @@ int gm_probe_hbm_copy_variant(int dev, int variant, uint64_t bytes, int iters,
   if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
   if (!e) e = (int)hipEventSynchronize(ev.e1);
   float ms = 0;
-  if (!e) e = (int)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+  if (!e) e = elapsed_ms(ev.e0, ev.e1, &ms);
   if (!e && ms > 0) *gbps = 2.0 * (double)bytes * iters / (ms * 1e-3) / 1e9;
   return e;
 }
@@ -502,7 +494,7 @@ int gm_probe_hbm_read(int dev, uint64_t bytes, int iters, int blocks_per_cu, dou
   if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
   if (!e) e = (int)hipEventSynchronize(ev.e1);
   float ms = 0;
-  if (!e) e = (int)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+  if (!e) e = elapsed_ms(ev.e0, ev.e1, &ms);
   if (!e && ms > 0) *gbps = (double)bytes * iters / (ms * 1e-3) / 1e9;
   return e;
 }
@@ -534,7 +526,7 @@ int gm_probe_mfma_peak_variant(int dev, int variant, int iters, int blocks_per_c
   (void)hipEventRecord(b, 0);
   hipError_t e = hipEventSynchronize(b);
   float ms = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
+  if (e == hipSuccess) e = (hipError_t)elapsed_ms(a, b, &ms);
   const double per = variant ? 2.0 * 16 * 16 * 32 : 2.0 * 32 * 32 * 16;
   const double chains = variant == 2 ? 8.0 : 4.0;
   const double flops = per * chains * iters * (double)blocks * 4 /* waves */;
@@ -648,7 +640,7 @@ int gm_probe_p2p(int dev_a, int dev_b, uint64_t bytes, int iters, int* can_acces
   (void)hipEventRecord(b, st);
   if (e == hipSuccess) e = hipEventSynchronize(b);
   float ms = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
+  if (e == hipSuccess) e = (hipError_t)elapsed_ms(a, b, &ms);
   if (e == hipSuccess && ms > 0) *gbps = (double)bytes * iters / (ms * 1e-3) / 1e9;
   (void)hipEventDestroy(a);
   (void)hipEventDestroy(b);

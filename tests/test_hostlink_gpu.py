@@ -5,9 +5,9 @@ negative control, and the command lines. Nothing here holds more than 16 MiB of 
 
 Geometry the shapes rely on (gm_hostlink.hip): 16-byte elements, 256-thread blocks, a step of
 ``STEP`` bytes per block, each block's chunk a whole number of steps, blocks whose chunk starts
-past the end return. ``BIG`` = 6 steps + 4112 bytes runs, with 3 blocks, as two blocks of three
+past the end are not launched. ``BIG`` = 6 steps + 4112 bytes runs, with 3 blocks, as two blocks of three
 full steps and one block that has only the 16-byte tail loop (257 elements); with the default
-grid as six one-step blocks, the tail-only block and idle ones; with 1 block as one chunk."""
+grid as six one-step blocks and the tail-only block; with 1 block as one chunk."""
 import json
 import math
 import os
@@ -146,16 +146,14 @@ def test_kread_reports_exactly_the_planted_flips(bufs, count, invert):
             assert all(x["pattern"] == "random" and x["pass"] == 2 for x in r["first_errors"])
 
 
-def test_every_load_of_a_step_is_compared(bufs):
-    """One flip at a time in each of the U loads a lane has in flight in a full step (the first
-    word, the last word and the tail are covered above), in both words of the 16-byte element,
-    for the reading kernel and for the copying one."""
-    loads = STEP // 4096                                         # U: 4 KiB per load and block
-    for nbytes, step in ((STEP + 16, 0), (BIG, 1)):
+def _every_load_of_a_step_is_compared(bufs, step_bytes):
+    """``bufs``: (source, destination) by size, for one step + 16 B and six steps + 4112 B."""
+    loads = step_bytes // 4096                                   # U: 4 KiB per load and block
+    for nbytes, step in ((step_bytes + 16, 0), (6 * step_bytes + 4112, 1)):
         src, dst = bufs[nbytes]
         want = _want("random", False, 0, 0, nbytes)
         for c in range(loads):
-            off = step * STEP + c * 4096 + 16 * ((37 * c + 5) % 256) + 8 * (c & 1)
+            off = step * step_bytes + c * 4096 + 16 * ((37 * c + 5) % 256) + 8 * (c & 1)
             src.data[:] = want
             src.data[off // 8] ^= np.uint64(1 << c)
             planted = {(off, int(want[off // 8]), int(want[off // 8]) ^ (1 << c))}
@@ -165,6 +163,58 @@ def test_every_load_of_a_step_is_compared(bufs):
                 r = hostlink.kcopy(src.body, dst.body, "random", seed=SEED, blocks=blocks)
                 assert r["errors"] == 1 and _records(r) == planted, (nbytes, c, blocks, r)
                 assert np.array_equal(dst.data, src.data)
+
+
+def test_every_load_of_a_step_is_compared(bufs):
+    """One flip at a time in each of the U loads a lane has in flight in a full step (the first
+    word, the last word and the tail are covered above), in both words of the 16-byte element,
+    for the reading kernel and for the copying one."""
+    assert BIG == 6 * STEP + 4112
+    _every_load_of_a_step_is_compared(bufs, STEP)
+
+
+@pytest.fixture
+def unroll4():
+    """The kernels with 4 loads in flight (bench/hostlink_rates.py sweeps both); yields their
+    step in bytes and puts the unroll back."""
+    lib = _native.probe()
+    was = lib.gm_probe_hostlink_unroll(4)
+    try:
+        step = hostlink.geometry()["step_bytes"]
+        assert step == 4 * 256 * 16
+        yield step
+    finally:
+        lib.gm_probe_hostlink_unroll(was)
+        assert hostlink.geometry()["step_bytes"] == STEP
+
+
+@pytest.mark.parametrize("pattern", memtest.ALL_PATTERNS)
+def test_unroll_4_kernels_write_read_and_copy(unroll4, pattern):
+    """Every size class again with the 16 KiB step: only a tail, less than a step, one step and
+    a tail element, and six steps + 4112 B (with 3 blocks: two of three steps and a tail-only
+    one)."""
+    for nbytes in (16, 4096 - 16, unroll4 + 16, 6 * unroll4 + 4112):
+        src, dst = Pinned(nbytes), Pinned(nbytes)
+        want = _want(pattern, False, 3, 4096, nbytes)
+        for blocks in BLOCKS:
+            src.words[:] = GUARD_WORD
+            dst.words[:] = GUARD_WORD
+            hostlink.kwrite(src.body, pattern, seed=SEED, pass_=3, base_offset=4096, blocks=blocks)
+            torch.cuda.synchronize()
+            assert np.array_equal(src.data, want) and src.guards_intact(), (nbytes, blocks)
+            r = hostlink.kread(src.body, pattern, seed=SEED, pass_=3, base_offset=4096,
+                               blocks=blocks)
+            assert r["ok"] and r["errors"] == 0 and r["bytes"] == nbytes, (nbytes, blocks, r)
+            r = hostlink.kcopy(src.body, dst.body, pattern, seed=SEED, pass_=3, base_offset=4096,
+                               blocks=blocks)
+            assert r["ok"] and r["errors"] == 0 and r["bytes"] == nbytes, (nbytes, blocks, r)
+            assert np.array_equal(dst.data, want) and np.array_equal(src.data, want)
+            assert dst.guards_intact() and src.guards_intact(), (nbytes, blocks)
+
+
+def test_unroll_4_every_load_of_a_step_is_compared(unroll4):
+    sizes = (unroll4 + 16, 6 * unroll4 + 4112)
+    _every_load_of_a_step_is_compared({n: (Pinned(n), Pinned(n)) for n in sizes}, unroll4)
 
 
 @pytest.mark.parametrize("pattern", ("addr", "walk", "random"))

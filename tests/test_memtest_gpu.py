@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+from gpumounter_amd import _native
 from gpumounter_amd.ops import memtest
 
 pytestmark = pytest.mark.gpu
@@ -59,9 +60,7 @@ def _flip(t, flips) -> None:
     t[idx] = t[idx] ^ masks
 
 
-@pytest.mark.parametrize("invert", [False, True])
-@pytest.mark.parametrize("pattern", memtest.ALL_PATTERNS)
-def test_fill_matches_the_host_reference(pattern, invert):
+def _fill_matches_the_host_reference(pattern, invert):
     for nbytes in SIZES:
         t = _buf(nbytes + 32)
         t.fill_(0x1111111111111111)
@@ -71,6 +70,12 @@ def test_fill_matches_the_host_reference(pattern, invert):
         np.testing.assert_array_equal(got[2:-2], _want(pattern, invert, 3, 0, nbytes),
                                       err_msg=f"{pattern} invert={invert} {nbytes} B")
         assert (got[:2] == 0x1111111111111111).all() and (got[-2:] == 0x1111111111111111).all()
+
+
+@pytest.mark.parametrize("invert", [False, True])
+@pytest.mark.parametrize("pattern", memtest.ALL_PATTERNS)
+def test_fill_matches_the_host_reference(pattern, invert):
+    _fill_matches_the_host_reference(pattern, invert)
 
 
 @pytest.mark.parametrize("pattern", memtest.ALL_PATTERNS)
@@ -134,13 +139,13 @@ def test_verify_keeps_16_records_of_40_errors():
         assert int(x["xor"], 16) == 1 << (offs.index(x["offset"]) % 64)
 
 
-@pytest.mark.parametrize("pattern", ["addr", "solid", "random"])
-def test_verify_and_invert_leaves_the_inverse_everywhere(pattern):
+def _verify_and_invert_leaves_the_inverse_everywhere(pattern):
     t = _buf(BIG)
     memtest.fill(t, pattern, seed=SEED, pass_=1)
     _flip(t, FLIPS)
     r = memtest.verify(t, pattern, write_inverse=True, seed=SEED, pass_=1)
     assert r["errors"] == len(FLIPS)
+    assert r["bit_errors"] == sum(bin(m).count("1") for _, m in FLIPS)
     np.testing.assert_array_equal(_host(t), _want(pattern, True, 1, 0, BIG))
     again = memtest.verify(t, pattern, invert=True, seed=SEED, pass_=1)
     assert again["errors"] == 0 and again["first_errors"] == []
@@ -148,6 +153,28 @@ def test_verify_and_invert_leaves_the_inverse_everywhere(pattern):
     r = memtest.verify(t, pattern, invert=True, write_inverse=True, seed=SEED, pass_=1)
     assert r["errors"] == 0
     np.testing.assert_array_equal(_host(t), _want(pattern, False, 1, 0, BIG))
+
+
+@pytest.mark.parametrize("pattern", ["addr", "solid", "random"])
+def test_verify_and_invert_leaves_the_inverse_everywhere(pattern):
+    _verify_and_invert_leaves_the_inverse_everywhere(pattern)
+
+
+@pytest.mark.parametrize("pattern", memtest.ALL_PATTERNS)
+def test_plain_store_kernels_fill_and_invert_like_the_nontemporal_ones(pattern):
+    """The writing kernels exist twice, with nontemporal (the default) and with plain stores
+    (bench/memtest_rates.py times both): the same shapes, flips and expectations for the
+    plain-store ones."""
+    lib = _native.probe()
+    was = lib.gm_probe_memtest_store_variant(0)
+    try:
+        assert lib.gm_probe_memtest_store_variant(-1) == 0
+        for invert in (False, True):
+            _fill_matches_the_host_reference(pattern, invert)
+        _verify_and_invert_leaves_the_inverse_everywhere(pattern)
+    finally:
+        lib.gm_probe_memtest_store_variant(was)
+    assert lib.gm_probe_memtest_store_variant(-1) == was
 
 
 def test_uint8_and_uint64_tensors_are_accepted():
