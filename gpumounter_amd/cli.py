@@ -20,6 +20,10 @@
                                        [--atomics-rounds N]                  # cross-XCC atomics
                                        [--atomics-inject add:KIND:G:S:MASK|cas:G:S:MASK|
                                                          ticket:G:S|handoff:BLOCK:ROUND:WORD:MASK]
+                                       [--mfma-scan] [--mfma-scan-formats f16,fp8,...,mxfp4]
+                                       [--mfma-scan-iters N] [--mfma-scan-rounds N]
+                                       [--mfma-scan-inject ID|any:FORMAT:THREAD:WORD:MASK]
+                                                                # per-CU matrix-core format scan
     python -m gpumounter_amd add    --master URL --ns NS --pod P -n 2 [--entire] [--lease 3600]
     python -m gpumounter_amd remove --master URL --ns NS --pod P --uuid U [--uuid U2] [--force]
     python -m gpumounter_amd status --master URL --node NODE
@@ -27,6 +31,7 @@
     python -m gpumounter_amd doctor  [--json] [--skip-cluster] [--gpu [--burn-in 30]]  # preflight
                                      [--gpu --memtest [SIZE]] [--gpu --cu-scan]
                                      [--gpu --host-link [SIZE]] [--gpu --atomics]
+                                     [--gpu --mfma-scan]
     python -m gpumounter_amd config-doc > docs/CONFIG.md   # every GM_* setting, from the source
 
 The reference ships only the two daemons and documents curl calls (QuickStart.md:41-92); the
@@ -223,6 +228,27 @@ def _add_atomics(p, what: str) -> None:
                         "handoff:BLOCK:ROUND:WORD:MASK; the test must report it")
 
 
+def _mfmascan_arg(kind):
+    """argparse type for the --mfma-scan-* options: the parser in ops.mfmascan, its refusal a
+    usage error."""
+    def conv(text):
+        from gpumounter_amd.ops import mfmascan
+        try:
+            return getattr(mfmascan, kind)(text)
+        except mfmascan.ProbeError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    conv.__name__ = kind
+    return conv
+
+
+def _add_mfmascan(p, what: str) -> None:
+    p.add_argument("--mfma-scan", action="store_true", help=what)
+    p.add_argument("--mfma-scan-inject", type=_mfmascan_arg("parse_inject"), default=None,
+                   metavar="ID|any:FORMAT:THREAD:WORD:MASK",
+                   help="negative control: flip that accumulator word of that format on that CU; "
+                        "the scan must name it")
+
+
 HOSTLINK_AUTO = -1    # --host-link without a SIZE: the test's default size
 
 
@@ -320,6 +346,29 @@ def cmd_probe(args) -> int:
             print(f"probe: --atomics-inject into {inj[0]!r}, which --atomics-tests leaves out",
                   file=sys.stderr)
             return 2
+    if not args.mfma_scan:
+        given = [o for o, v in (("--mfma-scan-inject", args.mfma_scan_inject),
+                                ("--mfma-scan-formats", args.mfma_scan_formats),
+                                ("--mfma-scan-iters", args.mfma_scan_iters),
+                                ("--mfma-scan-rounds", args.mfma_scan_rounds)) if v is not None]
+        if given:
+            print(f"probe: {given[0]} needs --mfma-scan", file=sys.stderr)
+            return 2
+    else:
+        from gpumounter_amd.ops import mfmascan as _ms
+
+        if args.mfma_scan_iters is not None and not 1 <= args.mfma_scan_iters <= _ms.MAX_ITERS:
+            print(f"probe: --mfma-scan-iters must be between 1 and {_ms.MAX_ITERS}",
+                  file=sys.stderr)
+            return 2
+        if args.mfma_scan_rounds is not None and not 1 <= args.mfma_scan_rounds <= 1024:
+            print("probe: --mfma-scan-rounds must be between 1 and 1024", file=sys.stderr)
+            return 2
+        inj = args.mfma_scan_inject
+        if inj and args.mfma_scan_formats is not None and inj[1] not in args.mfma_scan_formats:
+            print(f"probe: --mfma-scan-inject into {inj[1]!r}, which --mfma-scan-formats leaves "
+                  f"out", file=sys.stderr)
+            return 2
     if args.bdf:
         bdfs = args.bdf
     else:
@@ -368,6 +417,16 @@ def cmd_probe(args) -> int:
                 rounds=args.atomics_rounds or atomics.DEFAULT_ROUNDS,
                 _inject=args.atomics_inject)
             bad |= not r["atomics"]["ok"]
+    if args.mfma_scan:
+        from gpumounter_amd.ops import mfmascan
+
+        rounds = args.mfma_scan_rounds or 1
+        for r in res:
+            r["mfmascan"] = mfmascan.scan(
+                r["device"], formats=args.mfma_scan_formats or mfmascan.ALL_FORMATS,
+                iters=args.mfma_scan_iters or mfmascan.DEFAULT_ITERS, min_rounds=rounds,
+                max_rounds=max(16, rounds), _inject=args.mfma_scan_inject)
+            bad |= not r["mfmascan"]["ok"]
     print(json.dumps(res, indent=2))
     return 1 if bad else 0
 
@@ -532,9 +591,16 @@ def cmd_doctor(args) -> int:
         extra["atomics"] = True
         if args.atomics_inject:
             extra["atomics_inject"] = args.atomics_inject
+    if args.mfma_scan_inject and not args.mfma_scan:
+        print("doctor: --mfma-scan-inject needs --mfma-scan", file=sys.stderr)
+        return 2
+    if args.mfma_scan:
+        extra["mfma_scan"] = True
+        if args.mfma_scan_inject:
+            extra["mfma_scan_inject"] = args.mfma_scan_inject
     checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
                         gpu=(args.gpu or bool(args.burn_in) or bool(memtest_bytes) or args.cu_scan
-                             or args.host_link is not None or args.atomics),
+                             or args.host_link is not None or args.atomics or args.mfma_scan),
                         burn_in_s=args.burn_in, memtest_bytes=memtest_bytes,
                         cu_scan=args.cu_scan, **extra)
     print(doctor.render(checks, args.json))
@@ -621,6 +687,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="blocks of 256 threads, 1..4096 (default: one per CU)")
     p.add_argument("--atomics-rounds", type=int, default=None, metavar="N",
                    help="hand-off rounds, 1..64 (default 8)")
+    _add_mfmascan(p, "per-CU matrix-core format scan of every probed GPU: bit-exact MFMAs in "
+                     "f16, fp8, bf8, i8, f32, f64 and the block-scaled fp8, bf8, fp6, bf6 and fp4 "
+                     "forms on every compute unit (exit 1 on any wrong word)")
+    p.add_argument("--mfma-scan-formats", type=_mfmascan_arg("parse_formats"), default=None,
+                   metavar="a,b,...",
+                   help="of f16,fp8,bf8,i8,f32,f64,mxfp8,mxbf8,mxfp6,mxbf6,mxfp4 (default: all)")
+    p.add_argument("--mfma-scan-iters", type=int, default=None, metavar="N",
+                   help="dependent MFMAs per wave and format, 1..63 (default 16)")
+    p.add_argument("--mfma-scan-rounds", type=int, default=None, metavar="N",
+                   help="at least N rounds (a round is one block per CU)")
     p.set_defaults(fn=cmd_probe)
     for name, fn in (("add", cmd_add), ("remove", cmd_remove), ("status", cmd_status)):
         p = sub.add_parser(name)
@@ -663,6 +739,8 @@ def build_parser() -> argparse.ArgumentParser:
     _add_hostlink_size(p, "with --gpu: host link (PCIe) test of every GPU over SIZE bytes of "
                           "pinned host memory per buffer (default 256M)")
     _add_atomics(p, "with --gpu: cross-XCC atomics and coherence test of every GPU")
+    _add_mfmascan(p, "with --gpu: per-CU matrix-core format scan of every GPU; a failing CU "
+                     "is named with the format")
     p.set_defaults(fn=cmd_doctor)
     p = sub.add_parser("bpf-dump")
     p.add_argument("--allow", action="append", default=[])

@@ -164,10 +164,6 @@ def _simds(mask: int):
     return [i for i in range(4) if mask >> i & 1]
 
 
-def _test_names(mask: int):
-    return [n for n in TESTS if TESTS[n] & mask]
-
-
 def scan(dev: int, tests=ALL_TESTS, iters: int = DEFAULT_ITERS, seed: int = DEFAULT_SEED,
          min_rounds: int = 1, max_rounds: int = 16, _inject=None) -> Dict:
     """The scan of device ``dev``. A round is one launch of as many blocks as the device has CUs;
@@ -191,22 +187,36 @@ def scan(dev: int, tests=ALL_TESTS, iters: int = DEFAULT_ITERS, seed: int = DEFA
         dev, mask, iters, seed, min_rounds, max_rounds,
         C.byref(inj) if inj is not None else None, C.byref(res), cus,
         _native.CUSCAN_IDS, C.byref(n)), "cu-scan")
+    return decode_result(dev, mask, iters, res, cus, n.value, TESTS, "tests")
+
+
+def decode_result(dev: int, mask: int, iters: int, res, cus, n: int, bits: Dict[str, int],
+                  key: str) -> Dict:
+    """The result dict of a scan in the CU scan's frame (this one and
+    :mod:`gpumounter_amd.ops.mfmascan`) from the C structures; ``bits`` names the test bits and
+    ``key`` is what the list of the tests that ran is called (``"tests"`` here, hence ``"test"`` in
+    a record and ``"tests_failed"`` per CU)."""
+    names = {v: k for k, v in bits.items()}
+
+    def named(m: int):
+        return [k for k, v in bits.items() if v & m]
+
     per_cu = []
-    for i in range(min(n.value, _native.CUSCAN_IDS)):
+    for i in range(min(n, _native.CUSCAN_IDS)):
         c = cus[i]
         per_cu.append({"id": c.id, "xcc": c.xcc, "se": c.se, "sh": c.sh, "cu": c.cu,
                        "runs": c.runs, "failed_runs": c.failed_runs,
-                       "tests_failed": _test_names(c.tests_failed),
+                       f"{key}_failed": named(c.tests_failed),
                        "simds_seen": _simds(c.simds_seen),
                        "simds_failed": _simds(c.simds_failed)})
     records = []
     for i in range(res.records_filled):
         r = res.records[i]
         records.append({"id": r.id, **decode_id(r.id & (_native.CUSCAN_IDS - 1)), "simd": r.simd,
-                        "test": TEST_NAMES.get(r.test, str(r.test)), "thread": r.thread,
+                        key[:-1]: names.get(r.test, str(r.test)), "thread": r.thread,
                         "word": r.word, "expected": f"{r.expected:#010x}",
                         "got": f"{r.got:#010x}", "xor": f"{r.expected ^ r.got:#010x}"})
-    return {"device": dev, "tests": _test_names(mask), "iters": iters,
+    return {"device": dev, key: named(mask), "iters": iters,
             "cus_expected": res.cus_expected, "cus_seen": res.cus_seen,
             "complete": bool(res.complete), "rounds": res.rounds, "blocks_run": res.blocks_run,
             "words_in_error": res.words_in_error, "failed_cus": res.failed_cus,
@@ -214,16 +224,16 @@ def scan(dev: int, tests=ALL_TESTS, iters: int = DEFAULT_ITERS, seed: int = DEFA
             "xcc_cus": list(res.xcc_cus), "seconds": res.seconds, "kernel_ms": res.kernel_ms,
             "first_errors": records,
             "failed": [{k: c[k] for k in ("id", "xcc", "se", "sh", "cu", "runs", "failed_runs",
-                                          "tests_failed", "simds_failed")}
+                                          f"{key}_failed", "simds_failed")}
                        for c in per_cu if c["failed_runs"]],
             "per_cu": per_cu, "ok": res.words_in_error == 0}
 
 
-def describe_failed(result: Dict) -> str:
+def describe_failed(result: Dict, key: str = "tests") -> str:
     """One line naming the failed units of a :func:`scan` result (the first four, then how many
-    more), for ``doctor``."""
+    more), for ``doctor``; ``key`` as in :func:`decode_result`."""
     failed = result["failed"]
     text = "; ".join(f"xcc {c['xcc']} se {c['se']} sh {c['sh']} cu {c['cu']} (id {c['id']:#05x}) "
                      f"simd {','.join(map(str, c['simds_failed']))} "
-                     f"{'+'.join(c['tests_failed'])}" for c in failed[:4])
+                     f"{'+'.join(c[key + '_failed'])}" for c in failed[:4])
     return text + (f"; and {len(failed) - 4} more" if len(failed) > 4 else "")

@@ -22,7 +22,10 @@ starting a job on them — the reference offers nothing here:
    and each GPU in both directions, by the copy engines and by kernels, with per-leg GB/s;
 8. optionally (``--atomics``) the cross-XCC atomics and coherence test on all GPUs at once
    (:func:`gpumounter_amd.ops.atomics.run`): known-answer atomics of ten kinds, tickets, a CAS
-   loop and in-launch hand-offs between blocks with the agent-scope release and acquire.
+   loop and in-launch hand-offs between blocks with the agent-scope release and acquire;
+9. optionally (``--mfma-scan``) the per-CU matrix-core format scan on all GPUs at once
+   (:func:`gpumounter_amd.ops.mfmascan.scan`): bit-exact MFMAs in f16, fp8, bf8, i8, f32, f64 and
+   the block-scaled fp8, bf8, fp6, bf6 and fp4 forms on every compute unit.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -95,7 +98,21 @@ def main(argv=None) -> int:
                     help="then the cross-XCC atomics and coherence test on every GPU at once")
     ap.add_argument("--atomics-inject", default=None, metavar="TEST:...",
                     help="its negative control (see probe --atomics-inject); needs --atomics")
+    ap.add_argument("--mfma-scan", action="store_true",
+                    help="then the per-CU matrix-core format scan on every GPU at once")
+    ap.add_argument("--mfma-scan-inject", default=None,
+                    metavar="ID|any:FORMAT:THREAD:WORD:MASK",
+                    help="its negative control (see probe --mfma-scan-inject); needs --mfma-scan")
     args = ap.parse_args(argv)
+    mfma_scan_inject = None
+    if args.mfma_scan_inject is not None:
+        from gpumounter_amd.ops import mfmascan
+        if not args.mfma_scan:
+            ap.error("--mfma-scan-inject needs --mfma-scan")
+        try:
+            mfma_scan_inject = mfmascan.parse_inject(args.mfma_scan_inject)
+        except mfmascan.ProbeError as e:
+            ap.error(str(e))
     atomics_inject = None
     if args.atomics_inject is not None:
         from gpumounter_amd.ops import atomics
@@ -199,6 +216,17 @@ def main(argv=None) -> int:
             #                               "first_errors" names the XCCs then
         report["atomics"] = at
         report["ok"] &= all(a["ok"] for a in at)
+    if args.mfma_scan and not args.cpu_ranks:
+        from concurrent.futures import ThreadPoolExecutor
+
+        from gpumounter_amd.ops import mfmascan
+
+        with ThreadPoolExecutor(max_workers=world) as ex:
+            ms = list(ex.map(lambda d: mfmascan.scan(d, _inject=mfma_scan_inject), range(world)))
+        for m in ms:
+            del m["per_cu"]               # as for the CU scan: "failed" names the bad ones
+        report["mfmascan"] = ms
+        report["ok"] &= all(m["ok"] for m in ms)
     print(json.dumps(report))
     return 0 if report["ok"] else 1
 

@@ -284,7 +284,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                memtest_flip=None, burn_in_flip=None, cu_scan: bool = False,
                cu_scan_inject=None, host_link_bytes: int = 0,
                host_link_flip=None, atomics: bool = False,
-               atomics_inject=None) -> List[Check]:
+               atomics_inject=None, mfma_scan: bool = False,
+               mfma_scan_inject=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
@@ -301,8 +302,11 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     coherence test (:func:`gpumounter_amd.ops.atomics.run`): a wrong table word, a lost or doubled
     ticket, a given-up CAS or a stale or lost hand-off word fails the check and is named; hand-offs
     not seen within the budget do not, but when none at all was seen the check warns that the
-    hand-off proved nothing; ``atomics_inject`` is its negative control. A GPU that fails here
-    should not be handed out."""
+    hand-off proved nothing; ``atomics_inject`` is its negative control. With ``mfma_scan`` also
+    the per-CU matrix-core format scan (:func:`gpumounter_amd.ops.mfmascan.scan`): a CU with a
+    wrong accumulator word fails the check and is named as the CU scan names it, with the format;
+    ``mfma_scan_inject`` is its negative control. A GPU that fails here should not be handed
+    out."""
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import probe
 
@@ -388,6 +392,18 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                 elif a["handoff_vacuous"]:
                     detail += ", no hand-off was seen within the budget: it proved nothing"
                     status = "warn" if status == "ok" else status
+            if mfma_scan:
+                from gpumounter_amd.ops import mfmascan
+
+                m = mfmascan.scan(d, _inject=mfma_scan_inject)
+                detail += (f", mfma-scan {len(m['formats'])} formats {m['cus_seen']}/"
+                           f"{m['cus_expected']} CUs in {m['rounds']} round(s) "
+                           f"{m['kernel_ms']:.2f} ms {m['words_in_error']} wrong words")
+                if not m["complete"]:
+                    detail += " (incomplete: not every CU was reached)"
+                if not m["ok"]:
+                    detail += f", failed: {mfmascan.describe_failed(m)}"
+                    status = "fail"
             out.append(Check(f"gpu{d}", status, detail))
         except Exception as e:  # noqa: BLE001 - a faulting GPU is exactly what this finds
             out.append(Check(f"gpu{d}", "fail", f"probe failed: {e}"))
@@ -399,7 +415,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
 
 def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         burn_in_s: float = 0.0, *, memtest_bytes: int = 0, cu_scan: bool = False,
-        host_link_bytes: int = 0, atomics: bool = False, atomics_inject=None) -> List[Check]:
+        host_link_bytes: int = 0, atomics: bool = False, atomics_inject=None,
+        mfma_scan: bool = False, mfma_scan_inject=None) -> List[Check]:
     checks = check_inventory(cfg) + check_cgroup(cfg) + check_devnodes(cfg) + \
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
@@ -410,6 +427,10 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
             extra["atomics"] = True
             if atomics_inject is not None:
                 extra["atomics_inject"] = atomics_inject
+        if mfma_scan:
+            extra["mfma_scan"] = True
+            if mfma_scan_inject is not None:
+                extra["mfma_scan_inject"] = mfma_scan_inject
         checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes, **extra)
     if not skip_cluster:
         async def both():

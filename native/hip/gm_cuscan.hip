@@ -8,95 +8,11 @@
 // observed, never assumed: the blocks share nothing but atomics into the result table and there
 // is no wait between them.
 //
-// The error path is cold, as in gm_memtest.hip: one OR per test on a healthy unit.
-#include "gm_probe.h"
-
-#include <hip/hip_runtime.h>
-#include <string.h>
-
-#include <vector>
-
-#include "gm_cuscan_sig.h"
-#include "gm_probe_common.h"
+// The frame (where a block runs, the compare, the bookkeeping, the round loop) is
+// gm_cuscan_frame.h, shared with the matrix-core format scan.
+#include "gm_cuscan_frame.h"
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// s_getreg immediate: (size - 1) << 11 | offset << 6 | register
-constexpr int kRegHwId = 4, kRegXccId = 20;
-constexpr int getreg(int size, int offset, int reg) {
-  return ((size - 1) << 11) | (offset << 6) | reg;
-}
-
-struct Slot {
-  uint32_t runs, failed_runs, tests_failed, simds_seen, simds_failed;
-};
-
-struct DevTable {
-  unsigned long long words, blocks, four_simds;
-  uint32_t distinct, claims;
-  gm_cuscan_record_t rec[GM_CUSCAN_MAX_RECORDS];
-  Slot slot[GM_CUSCAN_IDS];
-};
-
-struct Params {
-  uint64_t seed;
-  uint32_t tests, iters;
-  gm_cuscan_inject_t inj;  // mask 0: none
-};
-
-// Cold: entered per wrong word only.
-__device__ __noinline__ void report(DevTable* tab, uint32_t id, uint32_t simd, uint32_t test,
-                                    uint32_t thread, uint32_t word, uint32_t e, uint32_t g) {
-  const unsigned int slot = atomicAdd(&tab->claims, 1u);
-  if (slot < GM_CUSCAN_MAX_RECORDS) {
-    gm_cuscan_record_t* r = &tab->rec[slot];
-    r->id = id;
-    r->simd = simd;
-    r->test = test;
-    r->thread = thread;
-    r->word = word;
-    r->expected = e;
-    r->got = g;
-    r->pad = 0;
-  }
-}
-
-struct Where {
-  uint32_t id, simd;
-};
-
-// What became of one test's signature: the injected flip, then the compare (or the raw store).
-template <bool kCompare>
-__device__ __forceinline__ void finish(const Params& p, uint32_t test, int test_index,
-                                       const Where& at, uint32_t sig[4],
-                                       const uint32_t* __restrict__ expected, DevTable* tab,
-                                       uint32_t* sig_out, uint32_t& failed, uint32_t& bad) {
-  const uint32_t t = threadIdx.x;
-  if (p.inj.mask != 0 && p.inj.test == test && p.inj.thread == t &&
-      (p.inj.id == GM_CUSCAN_ANY || p.inj.id == at.id)) {
-#pragma unroll  // constant indices keep sig[] in registers
-    for (uint32_t i = 0; i < 4; ++i)
-      if (i == p.inj.word) sig[i] ^= p.inj.mask;
-  }
-  if constexpr (kCompare) {
-    const u32x4 e = ((const u32x4*)expected)[test_index * GM_CUSCAN_THREADS + t];
-    if (((sig[0] ^ e.x) | (sig[1] ^ e.y) | (sig[2] ^ e.z) | (sig[3] ^ e.w)) != 0) {
-      const uint32_t ev[4] = {e.x, e.y, e.z, e.w};
-#pragma unroll
-      for (uint32_t i = 0; i < 4; ++i)
-        if (sig[i] != ev[i]) {
-          report(tab, at.id, at.simd, test, t, i, ev[i], sig[i]);
-          ++bad;
-        }
-      failed |= test;
-    }
-  } else {
-    const u32x4 v = {sig[0], sig[1], sig[2], sig[3]};
-    ((u32x4*)sig_out)[t] = v;
-  }
-}
 
 __device__ __forceinline__ void test_mfma(uint64_t seed, uint32_t iters, uint32_t sig[4]) {
   const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -159,11 +75,8 @@ __global__ __launch_bounds__(GM_CUSCAN_THREADS) void k_cuscan(Params p,
                                                               DevTable* tab, uint32_t* sig_out,
                                                               uint32_t* where_out) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[GM_CUSCAN_LDS_WORDS];
-  const uint32_t t = threadIdx.x, w = t >> 6;
-  Where at;
-  at.id = (__builtin_amdgcn_s_getreg(getreg(4, 0, kRegXccId)) << 8) |
-          __builtin_amdgcn_s_getreg(getreg(8, 8, kRegHwId));
-  at.simd = __builtin_amdgcn_s_getreg(getreg(2, 4, kRegHwId));
+  const uint32_t t = threadIdx.x;
+  const Where at = where_am_i();
   uint32_t failed = 0, bad = 0;
   uint32_t sig[4];
   if (p.tests & GM_CUSCAN_VALU_INT) {
@@ -183,44 +96,7 @@ __global__ __launch_bounds__(GM_CUSCAN_THREADS) void k_cuscan(Params p,
     finish<kCompare>(p, GM_CUSCAN_LDS, 3, at, sig, expected, tab, sig_out, failed, bad);
   }
 
-  // the block's outcome: one leader lane per wave hands its wave's to thread 0 through the LDS,
-  // which the tests are done with
-  __syncthreads();
-  uint32_t wave_failed = failed, wave_bad = bad;
-  for (int off = 32; off > 0; off >>= 1) {
-    wave_failed |= __shfl_down(wave_failed, off, kWave);
-    wave_bad += __shfl_down(wave_bad, off, kWave);
-  }
-  if ((t & 63) == 0) {
-    lds[w] = at.simd;
-    lds[4 + w] = wave_failed;
-    lds[8 + w] = wave_bad;
-  }
-  __syncthreads();
-  if (t != 0) return;
-  uint32_t seen = 0, simds_failed = 0, tests_failed = 0, words = 0;
-  for (uint32_t i = 0; i < 4; ++i) {
-    seen |= 1u << (lds[i] & 3);
-    if (lds[4 + i]) simds_failed |= 1u << (lds[i] & 3);
-    tests_failed |= lds[4 + i];
-    words += lds[8 + i];
-  }
-  if constexpr (kCompare) {
-    Slot* s = &tab->slot[at.id & (GM_CUSCAN_IDS - 1)];
-    if (atomicAdd(&s->runs, 1u) == 0) atomicAdd(&tab->distinct, 1u);
-    atomicOr(&s->simds_seen, seen);
-    atomicAdd(&tab->blocks, 1ull);
-    if (__popc(seen) == 4) atomicAdd(&tab->four_simds, 1ull);
-    if (tests_failed) {
-      atomicAdd(&s->failed_runs, 1u);
-      atomicOr(&s->tests_failed, tests_failed);
-      atomicOr(&s->simds_failed, simds_failed);
-      atomicAdd(&tab->words, (unsigned long long)words);
-    }
-  } else {
-    where_out[0] = at.id;
-    for (uint32_t i = 0; i < 4; ++i) where_out[1 + i] = lds[i];
-  }
+  book_block<kCompare>(lds, at, failed, bad, tab, where_out);
 }
 
 bool one_test(uint32_t t) {
@@ -234,8 +110,7 @@ bool iters_ok(uint32_t tests, uint32_t iters) {
 }
 
 bool inject_ok(const gm_cuscan_inject_t* in, uint32_t tests) {
-  return one_test(in->test) && (in->test & tests) && in->thread < GM_CUSCAN_THREADS &&
-         in->word < 4 && in->mask != 0 && (in->id == GM_CUSCAN_ANY || in->id < GM_CUSCAN_IDS);
+  return one_test(in->test) && inject_fields_ok(in, tests);
 }
 
 }  // namespace
@@ -269,95 +144,22 @@ int gm_probe_cuscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed,
   memset(out, 0, sizeof(*out));
   if (n_cus) *n_cus = 0;
   if (tests_mask == 0 || (tests_mask & ~(uint32_t)GM_CUSCAN_ALL) || !iters_ok(tests_mask, iters) ||
-      min_rounds < 1 || max_rounds < min_rounds || max_rounds > 1024 || cus_cap < 0 ||
-      (cus_cap > 0 && !cus) || (inject && !inject_ok(inject, tests_mask)))
+      !rounds_ok(min_rounds, max_rounds, cus, cus_cap) ||
+      (inject && !inject_ok(inject, tests_mask)))
     return (int)hipErrorInvalidValue;
-  DeviceGuard g(dev);
-  if (!g.ok) return (int)hipErrorInvalidDevice;
-  const double t0 = now_s();
-  int cu_count = 0;
-  if (int e = current_cus(&cu_count)) return e;
-  if (cu_count <= 0) return (int)hipErrorInvalidDevice;
-
-  // the expectation comes from the host: a unit that computes wrongly must not produce its own
-  std::vector<uint32_t> h_exp(4 * GM_CUSCAN_SIG_WORDS, 0);
-  for (int i = 0; i < 4; ++i)
-    if (tests_mask & (1u << i))
-      gm_cuscan_expected_host(1u << i, seed, iters, &h_exp[(size_t)i * GM_CUSCAN_SIG_WORDS]);
-  DevBuf dexp, dtab;
-  GM_CHECK(dexp.alloc(h_exp.size() * sizeof(uint32_t)));
-  GM_CHECK(dtab.alloc(sizeof(DevTable)));
-  GM_CHECK(hipMemcpy(dexp.p, h_exp.data(), h_exp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  GM_CHECK(hipMemset(dtab.p, 0, sizeof(DevTable)));
-  Events ev;
-  GM_CHECK(ev.create());
-  {
-    // loads the code object here, not between a timed pair of events
-    hipFuncAttributes attr;
-    GM_CHECK(hipFuncGetAttributes(&attr, (const void*)k_cuscan<true>));
-  }
   Params p{};
   p.seed = seed;
   p.tests = tests_mask;
   p.iters = iters;
   if (inject) p.inj = *inject;
-  DevTable* tab = (DevTable*)dtab.p;
-
-  int rounds = 0;
-  uint32_t distinct = 0;
-  double ms_sum = 0;
-  while (rounds < max_rounds) {
-    GM_CHECK(hipEventRecord(ev.e0, nullptr));
-    hipLaunchKernelGGL(k_cuscan<true>, dim3((unsigned)cu_count), dim3(GM_CUSCAN_THREADS), 0,
-                       nullptr, p, (const uint32_t*)dexp.p, tab, (uint32_t*)nullptr,
-                       (uint32_t*)nullptr);
-    GM_CHECK(hipGetLastError());
-    GM_CHECK(hipEventRecord(ev.e1, nullptr));
-    GM_CHECK(hipMemcpy(&distinct, &tab->distinct, sizeof(distinct), hipMemcpyDeviceToHost));
-    float ms = 0;
-    if (int e = elapsed_ms(ev.e0, ev.e1, &ms)) return e;
-    ms_sum += ms;
-    ++rounds;
-    if (rounds >= min_rounds && distinct >= (uint32_t)cu_count) break;
-  }
-
-  std::vector<unsigned char> raw(sizeof(DevTable));
-  GM_CHECK(hipMemcpy(raw.data(), dtab.p, sizeof(DevTable), hipMemcpyDeviceToHost));
-  const DevTable* h = (const DevTable*)raw.data();
-  out->cus_expected = (uint32_t)cu_count;
-  out->rounds = (uint32_t)rounds;
-  out->blocks_run = h->blocks;
-  out->words_in_error = h->words;
-  out->blocks_four_simds = h->four_simds;
-  out->records_filled = h->claims < GM_CUSCAN_MAX_RECORDS ? h->claims : GM_CUSCAN_MAX_RECORDS;
-  for (uint32_t i = 0; i < out->records_filled; ++i) out->records[i] = h->rec[i];
-  int n = 0;
-  for (uint32_t id = 0; id < GM_CUSCAN_IDS; ++id) {
-    const Slot& s = h->slot[id];
-    if (s.runs == 0) continue;
-    ++out->cus_seen;
-    ++out->xcc_cus[id >> 8];
-    if (s.failed_runs) ++out->failed_cus;
-    if (n < cus_cap) {
-      gm_cuscan_cu_t* c = &cus[n];
-      c->id = id;
-      c->xcc = id >> 8;
-      c->se = (id >> 5) & 7;
-      c->sh = (id >> 4) & 1;
-      c->cu = id & 15;
-      c->runs = s.runs;
-      c->failed_runs = s.failed_runs;
-      c->tests_failed = s.tests_failed;
-      c->simds_seen = s.simds_seen;
-      c->simds_failed = s.simds_failed;
-    }
-    ++n;
-  }
-  if (n_cus) *n_cus = n;
-  out->complete = out->cus_seen == out->cus_expected;
-  out->kernel_ms = ms_sum;
-  out->seconds = now_s() - t0;
-  return 0;
+  return run_scan(
+      dev, k_cuscan<true>, p, 4 * GM_CUSCAN_SIG_WORDS,
+      [&](uint32_t* exp) {
+        for (int i = 0; i < 4; ++i)
+          if (tests_mask & (1u << i))
+            gm_cuscan_expected_host(1u << i, seed, iters, exp + (size_t)i * GM_CUSCAN_SIG_WORDS);
+      },
+      min_rounds, max_rounds, out, cus, cus_cap, n_cus);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // gm_probe_common.h — shared by the gfx950 probe translation units (gm_probe.hip, gm_gemm.hip,
-// gm_memtest.hip, gm_cuscan.hip, gm_hostlink.hip, gm_atomics.hip) and the block-scaled MFMA
-// experiment: vector types, device selection guard, error macro, owning device / pinned buffer,
-// stream and events, and the two clocks (event pair, host monotonic).
+// gm_memtest.hip, gm_cuscan.hip, gm_hostlink.hip, gm_atomics.hip, gm_mfmascan.hip) and the
+// block-scaled MFMA experiment: vector types, device selection guard, error macro, owning device /
+// pinned buffer, stream and events, and the two clocks (event pair, host monotonic).
 // Everything is in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
 

@@ -309,6 +309,74 @@ int gm_probe_cuscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed,
                     int max_rounds, const gm_cuscan_inject_t* inject, gm_cuscan_result_t* out,
                     gm_cuscan_cu_t* cus, int cus_cap, int* n_cus);
 
+// ------------------------------------------------------------------ matrix-core format scan
+// The CU scan's frame (one 256-thread block per CU, the whole LDS declared, the CU id read from
+// the registers, a host-computed table compared bit for bit) around the matrix cores in the
+// formats the CU scan's bf16 test leaves out. Every wave w = t / 64 runs `iters` dependent MFMAs
+// of each selected format; word i of lane l = t % 64 is the bit pattern of accumulator register i
+// (f64: lo ^ rotl32(hi, 16); i8: the int32). The code is gm_mfmascan_ref.h (shared by the host
+// and the kernel). H is the CU scan's hash; format index f = log2(bit).
+//
+//   bit   name   instruction                                         K    elements per lane
+//      1  f16    v_mfma_f32_16x16x32_f16                              32    8 half words
+//      2  fp8    v_mfma_f32_16x16x32_fp8_fp8 (OCP e4m3)               32    8 bytes
+//      4  bf8    v_mfma_f32_16x16x32_bf8_bf8 (e5m2)                   32    8 bytes
+//      8  i8     v_mfma_i32_16x16x64_i8                               64   16 bytes
+//     16  f32    v_mfma_f32_16x16x4_f32                                4    1
+//     32  f64    v_mfma_f64_16x16x4_f64                                4    1
+//     64  mxfp8  v_mfma_scale_f32_16x16x128_f8f6f4, cbsz = blgp = 0  128   32 bytes     (e4m3)
+//    128  mxbf8  the same, 1                                         128   32 bytes     (e5m2)
+//    256  mxfp6  the same, 2                                         128   32 x 6 bits  (e2m3)
+//    512  mxbf6  the same, 3                                         128   32 x 6 bits  (e3m2)
+//   1024  mxfp4  the same, 4                                         128   32 nibbles   (e2m1)
+//
+// Operands. Lane l's operand m (0: A, 1: B) in step s is built from the hash words
+//   h_q = H(0x200 + f, ((((4 s + w) * 2 + m) * 64 + l) * 4 + q),  q = 0..3
+// Nibble formats (f16, fp8, bf8, mx*): element e is nibble n = (h_{e >> 3} >> 4 (e & 7)) & 15 and
+// stands for the e2m1 value of n: magnitude (0, 1/2, 1, 3/2, 2, 3, 4, 6)[n & 7], negative when
+// n & 8 (so -0 occurs). The format's 16-entry code table encodes it: all 16 values are exact in
+// f16, e4m3, e5m2, e2m3 and e3m2; for mxfp4 the register image is h_0..h_3 itself. Packing:
+// 16-, 8- and 4-bit codes in element order from the low end of the lane's registers; 6-bit codes
+// as bits [6 e, 6 e + 6) of the 192-bit little-endian string of registers 0..5.
+//   i8:  the 16 bytes of h_0..h_3, signed, full range.
+//   f32: h_0 % 511 - 255;   f64: (h_0 & (2^23 - 1)) - 2^22.
+// mx* scales: the E8M0 byte of A's row i is 127 + (H(0x220 + f, (2 w + 0) * 16 + i) & 3) - 2, of
+// B's column j the same with (2 w + 1) * 16 + j: constant over the steps, the same in all four
+// lanes that hold the row (i, i + 16, i + 32, i + 48), byte 0 of the scale register, opsel 0.
+//
+// Expected value, over register images (a(l, e) = element e of lane l's A image):
+//   C[i][j] = sum over s < iters, h < 4, e of a_s(i + 16 h, e) * b_s(j + 16 h, e)
+//             (mx*: times 2^(sA_i + sB_j - 254))
+// and lane l register r holds C[4 (l >> 4) + r][l & 15] (f64: C[(l >> 4) + 4 r][l & 15]). This
+// rests on: lane l carries row / column l & 15 and K-group l >> 4; element e of a K-group names
+// the same k in A and in B; the C/D map above.
+//
+// Exactness: in quarter units a nibble product is at most 144, so 144 * K * iters < 2^24 keeps
+// every partial sum an exact fp32 in any order (iters <= 910 at K = 128), and the power-of-two
+// scale only moves the exponent. i8: 2^14 * 64 * iters < 2^31. f32: 4 * 255^2 * iters < 2^24
+// (iters <= 63). f64: 4 * 2^44 * iters < 2^53. One limit for all: GM_MFMASCAN_MAX_ITERS = 63
+// (static_asserts in gm_mfmascan_ref.h). A sum of zero is +0.0.
+//
+// Not covered: mixed A/B formats, the 32x32 shapes, v_smfmac_*, a different scale per K-block of
+// a row, NaN / infinity / subnormal operands, rounding (nothing here rounds).
+//
+// The records, the injection, the per-CU entries and the result are the CU scan's, with `test`
+// and `tests_failed` holding GM_MFMASCAN_* format bits. Arguments and the up-front
+// hipErrorInvalidValue checks are those of the gm_probe_cuscan* counterparts, with
+// 1 <= iters <= GM_MFMASCAN_MAX_ITERS.
+int gm_probe_mfmascan_expected(uint32_t format, uint64_t seed, uint32_t iters, uint32_t* out);
+// The operand register images the kernel feeds the instruction in step `step` (<
+// GM_MFMASCAN_MAX_ITERS): images[((w * 2 + m) * 64 + l) * 8 + d] = dword d of lane l's operand m
+// in wave w (4096 words), and scales[(w * 2 + m) * 16 + r] the E8M0 byte of row / column r (128
+// words; 127 for a format without scales). Host only, needs no GPU.
+int gm_probe_mfmascan_images(uint32_t format, uint64_t seed, uint32_t step, uint32_t* images,
+                             uint32_t* scales);
+int gm_probe_mfmascan_signature(uint32_t format, uint64_t seed, uint32_t iters, uint32_t* dev_out,
+                                uint32_t* dev_where, void* stream);
+int gm_probe_mfmascan(int dev, uint32_t formats_mask, uint32_t iters, uint64_t seed,
+                      int min_rounds, int max_rounds, const gm_cuscan_inject_t* inject,
+                      gm_cuscan_result_t* out, gm_cuscan_cu_t* cus, int cus_cap, int* n_cus);
+
 // ------------------------------------------------------------------ host link (PCIe) test
 // Moves checked bytes between pinned host memory and the GPU, in both directions, by the copy
 // engines (hipMemcpyAsync) and by kernels that read and write host memory through its device
