@@ -421,6 +421,12 @@ def probe() -> C.CDLL:
                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.gm_probe_mfmascan_signature.argtypes = lib.gm_probe_cuscan_signature.argtypes
         lib.gm_probe_mfmascan.argtypes = lib.gm_probe_cuscan.argtypes
+        lib.gm_probe_lanescan_expected.argtypes = lib.gm_probe_cuscan_expected.argtypes
+        lib.gm_probe_lanescan_lanes.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int),
+                                                C.POINTER(C.c_uint32)]
+        lib.gm_probe_lanescan_signature.argtypes = lib.gm_probe_cuscan_signature.argtypes
+        lib.gm_probe_lanescan.argtypes = lib.gm_probe_cuscan.argtypes
+        lib.gm_probe_lanescan_kernel_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.gm_probe_hostlink_geometry.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.gm_probe_hostlink_unroll.argtypes = [C.c_int]
         lib.gm_probe_hostlink_kwrite.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,

@@ -24,6 +24,10 @@
                                        [--mfma-scan-iters N] [--mfma-scan-rounds N]
                                        [--mfma-scan-inject ID|any:FORMAT:THREAD:WORD:MASK]
                                                                 # per-CU matrix-core format scan
+                                       [--lane-scan] [--lane-scan-tests xlane,regfile,...,packed]
+                                       [--lane-scan-iters N] [--lane-scan-rounds N]
+                                       [--lane-scan-inject ID|any:TEST:THREAD:WORD:MASK]
+                                                  # per-CU register, lane and scalar-unit scan
     python -m gpumounter_amd add    --master URL --ns NS --pod P -n 2 [--entire] [--lease 3600]
     python -m gpumounter_amd remove --master URL --ns NS --pod P --uuid U [--uuid U2] [--force]
     python -m gpumounter_amd status --master URL --node NODE
@@ -31,7 +35,7 @@
     python -m gpumounter_amd doctor  [--json] [--skip-cluster] [--gpu [--burn-in 30]]  # preflight
                                      [--gpu --memtest [SIZE]] [--gpu --cu-scan]
                                      [--gpu --host-link [SIZE]] [--gpu --atomics]
-                                     [--gpu --mfma-scan]
+                                     [--gpu --mfma-scan] [--gpu --lane-scan]
     python -m gpumounter_amd config-doc > docs/CONFIG.md   # every GM_* setting, from the source
 
 The reference ships only the two daemons and documents curl calls (QuickStart.md:41-92); the
@@ -249,6 +253,27 @@ def _add_mfmascan(p, what: str) -> None:
                         "the scan must name it")
 
 
+def _lanescan_arg(kind):
+    """argparse type for the --lane-scan-* options: the parser in ops.lanescan, its refusal a
+    usage error."""
+    def conv(text):
+        from gpumounter_amd.ops import lanescan
+        try:
+            return getattr(lanescan, kind)(text)
+        except lanescan.ProbeError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    conv.__name__ = kind
+    return conv
+
+
+def _add_lanescan(p, what: str) -> None:
+    p.add_argument("--lane-scan", action="store_true", help=what)
+    p.add_argument("--lane-scan-inject", type=_lanescan_arg("parse_inject"), default=None,
+                   metavar="ID|any:TEST:THREAD:WORD:MASK",
+                   help="negative control: flip that signature word of that test on that CU; "
+                        "the scan must name it")
+
+
 HOSTLINK_AUTO = -1    # --host-link without a SIZE: the test's default size
 
 
@@ -369,6 +394,29 @@ def cmd_probe(args) -> int:
             print(f"probe: --mfma-scan-inject into {inj[1]!r}, which --mfma-scan-formats leaves "
                   f"out", file=sys.stderr)
             return 2
+    if not args.lane_scan:
+        given = [o for o, v in (("--lane-scan-inject", args.lane_scan_inject),
+                                ("--lane-scan-tests", args.lane_scan_tests),
+                                ("--lane-scan-iters", args.lane_scan_iters),
+                                ("--lane-scan-rounds", args.lane_scan_rounds)) if v is not None]
+        if given:
+            print(f"probe: {given[0]} needs --lane-scan", file=sys.stderr)
+            return 2
+    else:
+        from gpumounter_amd.ops import lanescan as _ls
+
+        if args.lane_scan_iters is not None and not 1 <= args.lane_scan_iters <= _ls.MAX_ITERS:
+            print(f"probe: --lane-scan-iters must be between 1 and {_ls.MAX_ITERS}",
+                  file=sys.stderr)
+            return 2
+        if args.lane_scan_rounds is not None and not 1 <= args.lane_scan_rounds <= 1024:
+            print("probe: --lane-scan-rounds must be between 1 and 1024", file=sys.stderr)
+            return 2
+        inj = args.lane_scan_inject
+        if inj and args.lane_scan_tests is not None and inj[1] not in args.lane_scan_tests:
+            print(f"probe: --lane-scan-inject into {inj[1]!r}, which --lane-scan-tests leaves "
+                  f"out", file=sys.stderr)
+            return 2
     if args.bdf:
         bdfs = args.bdf
     else:
@@ -427,6 +475,16 @@ def cmd_probe(args) -> int:
                 iters=args.mfma_scan_iters or mfmascan.DEFAULT_ITERS, min_rounds=rounds,
                 max_rounds=max(16, rounds), _inject=args.mfma_scan_inject)
             bad |= not r["mfmascan"]["ok"]
+    if args.lane_scan:
+        from gpumounter_amd.ops import lanescan
+
+        rounds = args.lane_scan_rounds or 1
+        for r in res:
+            r["lanescan"] = lanescan.scan(
+                r["device"], tests=args.lane_scan_tests or lanescan.ALL_TESTS,
+                iters=args.lane_scan_iters or lanescan.DEFAULT_ITERS, min_rounds=rounds,
+                max_rounds=max(16, rounds), _inject=args.lane_scan_inject)
+            bad |= not r["lanescan"]["ok"]
     print(json.dumps(res, indent=2))
     return 1 if bad else 0
 
@@ -598,9 +656,17 @@ def cmd_doctor(args) -> int:
         extra["mfma_scan"] = True
         if args.mfma_scan_inject:
             extra["mfma_scan_inject"] = args.mfma_scan_inject
+    if args.lane_scan_inject and not args.lane_scan:
+        print("doctor: --lane-scan-inject needs --lane-scan", file=sys.stderr)
+        return 2
+    if args.lane_scan:
+        extra["lane_scan"] = True
+        if args.lane_scan_inject:
+            extra["lane_scan_inject"] = args.lane_scan_inject
     checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
                         gpu=(args.gpu or bool(args.burn_in) or bool(memtest_bytes) or args.cu_scan
-                             or args.host_link is not None or args.atomics or args.mfma_scan),
+                             or args.host_link is not None or args.atomics or args.mfma_scan
+                             or args.lane_scan),
                         burn_in_s=args.burn_in, memtest_bytes=memtest_bytes,
                         cu_scan=args.cu_scan, **extra)
     print(doctor.render(checks, args.json))
@@ -697,6 +763,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="dependent MFMAs per wave and format, 1..63 (default 16)")
     p.add_argument("--mfma-scan-rounds", type=int, default=None, metavar="N",
                    help="at least N rounds (a round is one block per CU)")
+    _add_lanescan(p, "per-CU register, lane and scalar-unit scan of every probed GPU: bit-exact "
+                     "cross-lane moves, a register-file march, a scalar chain, transcendentals at "
+                     "exact points, fp64 and packed arithmetic on every compute unit (exit 1 on "
+                     "any wrong word)")
+    p.add_argument("--lane-scan-tests", type=_lanescan_arg("parse_tests"), default=None,
+                   metavar="a,b,...", help="of xlane,regfile,salu,trans,f64,packed (default: all)")
+    p.add_argument("--lane-scan-iters", type=int, default=None, metavar="N",
+                   help="units of work per test, 1..63 (default 16)")
+    p.add_argument("--lane-scan-rounds", type=int, default=None, metavar="N",
+                   help="at least N rounds (a round is one block per CU)")
     p.set_defaults(fn=cmd_probe)
     for name, fn in (("add", cmd_add), ("remove", cmd_remove), ("status", cmd_status)):
         p = sub.add_parser(name)
@@ -741,6 +817,8 @@ def build_parser() -> argparse.ArgumentParser:
     _add_atomics(p, "with --gpu: cross-XCC atomics and coherence test of every GPU")
     _add_mfmascan(p, "with --gpu: per-CU matrix-core format scan of every GPU; a failing CU "
                      "is named with the format")
+    _add_lanescan(p, "with --gpu: per-CU register, lane and scalar-unit scan of every GPU; a "
+                     "failing CU is named with the test")
     p.set_defaults(fn=cmd_doctor)
     p = sub.add_parser("bpf-dump")
     p.add_argument("--allow", action="append", default=[])

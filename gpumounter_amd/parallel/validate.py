@@ -25,7 +25,11 @@ starting a job on them — the reference offers nothing here:
    loop and in-launch hand-offs between blocks with the agent-scope release and acquire;
 9. optionally (``--mfma-scan``) the per-CU matrix-core format scan on all GPUs at once
    (:func:`gpumounter_amd.ops.mfmascan.scan`): bit-exact MFMAs in f16, fp8, bf8, i8, f32, f64 and
-   the block-scaled fp8, bf8, fp6, bf6 and fp4 forms on every compute unit.
+   the block-scaled fp8, bf8, fp6, bf6 and fp4 forms on every compute unit;
+10. optionally (``--lane-scan``) the per-CU register, lane and scalar-unit scan on all GPUs at once
+   (:func:`gpumounter_amd.ops.lanescan.scan`): bit-exact cross-lane moves, a register-file march,
+   a scalar chain, transcendentals at exact points, fp64 and packed arithmetic on every compute
+   unit.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -103,7 +107,20 @@ def main(argv=None) -> int:
     ap.add_argument("--mfma-scan-inject", default=None,
                     metavar="ID|any:FORMAT:THREAD:WORD:MASK",
                     help="its negative control (see probe --mfma-scan-inject); needs --mfma-scan")
+    ap.add_argument("--lane-scan", action="store_true",
+                    help="then the per-CU register, lane and scalar-unit scan on every GPU at once")
+    ap.add_argument("--lane-scan-inject", default=None, metavar="ID|any:TEST:THREAD:WORD:MASK",
+                    help="its negative control (see probe --lane-scan-inject); needs --lane-scan")
     args = ap.parse_args(argv)
+    lane_scan_inject = None
+    if args.lane_scan_inject is not None:
+        from gpumounter_amd.ops import lanescan
+        if not args.lane_scan:
+            ap.error("--lane-scan-inject needs --lane-scan")
+        try:
+            lane_scan_inject = lanescan.parse_inject(args.lane_scan_inject)
+        except lanescan.ProbeError as e:
+            ap.error(str(e))
     mfma_scan_inject = None
     if args.mfma_scan_inject is not None:
         from gpumounter_amd.ops import mfmascan
@@ -227,6 +244,17 @@ def main(argv=None) -> int:
             del m["per_cu"]               # as for the CU scan: "failed" names the bad ones
         report["mfmascan"] = ms
         report["ok"] &= all(m["ok"] for m in ms)
+    if args.lane_scan and not args.cpu_ranks:
+        from concurrent.futures import ThreadPoolExecutor
+
+        from gpumounter_amd.ops import lanescan
+
+        with ThreadPoolExecutor(max_workers=world) as ex:
+            ls = list(ex.map(lambda d: lanescan.scan(d, _inject=lane_scan_inject), range(world)))
+        for m in ls:
+            del m["per_cu"]               # as for the CU scan: "failed" names the bad ones
+        report["lanescan"] = ls
+        report["ok"] &= all(m["ok"] for m in ls)
     print(json.dumps(report))
     return 0 if report["ok"] else 1
 

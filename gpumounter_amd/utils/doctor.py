@@ -285,7 +285,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                cu_scan_inject=None, host_link_bytes: int = 0,
                host_link_flip=None, atomics: bool = False,
                atomics_inject=None, mfma_scan: bool = False,
-               mfma_scan_inject=None) -> List[Check]:
+               mfma_scan_inject=None, lane_scan: bool = False,
+               lane_scan_inject=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
@@ -305,8 +306,11 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     hand-off proved nothing; ``atomics_inject`` is its negative control. With ``mfma_scan`` also
     the per-CU matrix-core format scan (:func:`gpumounter_amd.ops.mfmascan.scan`): a CU with a
     wrong accumulator word fails the check and is named as the CU scan names it, with the format;
-    ``mfma_scan_inject`` is its negative control. A GPU that fails here should not be handed
-    out."""
+    ``mfma_scan_inject`` is its negative control. With ``lane_scan`` also the per-CU register,
+    lane and scalar-unit scan (:func:`gpumounter_amd.ops.lanescan.scan`): a CU with a wrong
+    signature word fails the check and is named the same way, with the test; a scan that did not
+    reach every CU is stated, not failed; ``lane_scan_inject`` is its negative control. A GPU that
+    fails here should not be handed out."""
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import probe
 
@@ -404,6 +408,18 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                 if not m["ok"]:
                     detail += f", failed: {mfmascan.describe_failed(m)}"
                     status = "fail"
+            if lane_scan:
+                from gpumounter_amd.ops import lanescan
+
+                m = lanescan.scan(d, _inject=lane_scan_inject)
+                detail += (f", lane-scan {len(m['tests'])} tests {m['cus_seen']}/"
+                           f"{m['cus_expected']} CUs in {m['rounds']} round(s) "
+                           f"{m['kernel_ms']:.2f} ms {m['words_in_error']} wrong words")
+                if not m["complete"]:
+                    detail += " (incomplete: not every CU was reached)"
+                if not m["ok"]:
+                    detail += f", failed: {lanescan.describe_failed(m)}"
+                    status = "fail"
             out.append(Check(f"gpu{d}", status, detail))
         except Exception as e:  # noqa: BLE001 - a faulting GPU is exactly what this finds
             out.append(Check(f"gpu{d}", "fail", f"probe failed: {e}"))
@@ -416,7 +432,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
 def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         burn_in_s: float = 0.0, *, memtest_bytes: int = 0, cu_scan: bool = False,
         host_link_bytes: int = 0, atomics: bool = False, atomics_inject=None,
-        mfma_scan: bool = False, mfma_scan_inject=None) -> List[Check]:
+        mfma_scan: bool = False, mfma_scan_inject=None, lane_scan: bool = False,
+        lane_scan_inject=None) -> List[Check]:
     checks = check_inventory(cfg) + check_cgroup(cfg) + check_devnodes(cfg) + \
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
@@ -431,6 +448,10 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
             extra["mfma_scan"] = True
             if mfma_scan_inject is not None:
                 extra["mfma_scan_inject"] = mfma_scan_inject
+        if lane_scan:
+            extra["lane_scan"] = True
+            if lane_scan_inject is not None:
+                extra["lane_scan_inject"] = lane_scan_inject
         checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes, **extra)
     if not skip_cluster:
         async def both():

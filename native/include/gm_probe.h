@@ -241,7 +241,9 @@ int gm_probe_memtest_store_variant(int nontemporal);
 //                          in phase 3 was first written by the next wave; of the permuted reads
 //                          of phase 2 about three in four are of a word another wave wrote.
 //
-// What the scan cannot see: transcendental units, register-file addressing, clocks, thermals.
+// What the scan cannot see: clocks, thermals, the vector and instruction caches (the
+// transcendental units, register-file addressing, the scalar unit and the cross-lane network are
+// the lane scan's, below).
 // The GM_CUSCAN_* test bits and the iters limits are defined in gm_cuscan_sig.h.
 #define GM_CUSCAN_MAX_RECORDS 16
 #define GM_CUSCAN_IDS 4096
@@ -376,6 +378,134 @@ int gm_probe_mfmascan_signature(uint32_t format, uint64_t seed, uint32_t iters, 
 int gm_probe_mfmascan(int dev, uint32_t formats_mask, uint32_t iters, uint64_t seed,
                       int min_rounds, int max_rounds, const gm_cuscan_inject_t* inject,
                       gm_cuscan_result_t* out, gm_cuscan_cu_t* cus, int cus_cap, int* n_cus);
+
+// ------------------------------------------------------------------ lane scan
+// The CU scan's frame again (one 256-thread block per CU, so one wave per SIMD; the whole LDS
+// declared; the CU id read from the registers; a host-computed table compared bit for bit) around
+// what neither other scan reaches: the cross-lane network, register-file addressing, the scalar
+// unit, the transcendental pipe, fp64 vector arithmetic and the packed and dot instructions. Six
+// tests of 4 signature words per thread t (wave w = t / 64, lane l = t % 64). The code is
+// gm_lanescan_ref.h. What host and kernel share is data (hashes, operand values, menus of
+// immediates, folds); the operation under test is the instruction on the device and, on the host,
+// a plain model of what the ISA document says it does, so a unit that computes wrongly cannot
+// produce its own expected value. H is the CU scan's hash; fold(s, v) = rotl32(s, 5) + v.
+//
+//   bit  name     steps per unit of iters
+//     1  xlane    43 (the menu, once)
+//     2  regfile   1 round
+//     4  salu     16
+//     8  trans     8
+//    16  f64       8
+//    32  packed   16
+//
+// xlane. x_j = H(0x300, 4 t + j), j = 0..3. Step s: j = s & 3, menu entry
+// m = (s + H(0x301, 0) % 43) % 43, parameter g = H(0x301, 1 + s) (both uniform);
+//   moved = move_m(old = x_{(j + 1) & 3}, src = x_j)
+//   x_j   = (rotl32(moved + rotl32(x_j, 16), 9) ^ (l * 0x85EBCA6B + s)) * 0x9E3779B1
+// and the signature is x_0..x_3. The menu (GM_LANESCAN_DPP_MENU, GM_LANESCAN_SWIZZLE_MENU):
+//   0..28   v_mov_b32_dpp with the entry's dpp_ctrl, row_mask, bank_mask, bound_ctrl: quad_perm,
+//           row_shl / row_shr / row_ror, wave_shl / rol / shr / ror :1, row_mirror,
+//           row_half_mirror, row_bcast:15 (into rows 1, 3), row_bcast:31 (into rows 2, 3). A lane
+//           whose row or bank (lane % 16 / 4) is masked off keeps `old`; an enabled lane whose
+//           source is outside its row (or the wave) reads 0 with bound_ctrl, keeps `old` without.
+//   29..33  ds_swizzle_b32: offset bit 15 set: quad perm from bits 7:0; else lane
+//           ((l % 32 & and) | or) ^ xor of the lane's half, and | or << 5 | xor << 10
+//   34      ds_bpermute_b32 from lane (l (g | 1) + (g >> 8)) % 64
+//   35      ds_bpermute_b32 from lane ((l & g >> 14) + (g >> 20)) % 64 (many lanes read one)
+//   36      ds_permute_b32 to lane (l (g | 1) + (g >> 8)) % 64: a bijection, so no two lanes
+//           write one destination and no rule for collisions is relied on
+//   37, 38  v_readlane_b32 of lane g % 64; v_readfirstlane_b32 (lane 0: every lane is active)
+//   39      v_writelane_b32: old, with lane 21 (g % 4) set to src of lane (g >> 8) % 64
+//   40, 41  v_permlane16_swap / v_permlane32_swap (vdst = old, vsrc = src): rows 1 and 3 (the upper
+//           half) of vdst change places with rows 0 and 2 (the lower half) of vsrc; the result is
+//           new vdst + rotl32(new vsrc, 13)
+//   42      B = ballot of bit g % 32 of src: (old ^ lo(B) ^ hi(B)) + v_mbcnt (bits of B below l)
+//
+// regfile. A lane has 384 registers: 192 VGPRs in 6 banks of 32, indexed at run time within a
+// bank, and 192 accumulation registers behind v_accvgpr_write_b32 / _read_b32. reg_r = H(0x310,
+// 384 t + r). Per round q (iters rounds), with visit(r, i): s_{i & 3} = fold(s_{i & 3}, reg_r),
+// reg_r = ~reg_r:
+//   k = 0..11:  g = H(0x311, 16 q + k); visit(g % 192, k)                       (uniform index)
+//   k = 12..15: the same g; visit(32 (g % 6) + ((g >> 8) + l) % 32, k)          (index per lane)
+//   then visit(r, r) for r = 0..383 by constant index.
+// After the last round s_{r & 3} = fold(s_{r & 3}, reg_r) for r = 0..383; the signature is s_0..s_3.
+//
+// salu. One chain per wave on uniform values; T[i] = H(0x320, i), i < 1024, is read through a
+// const __restrict__ kernel argument. a = H(0x321, 4 w), b = H(0x321, 4 w + 1), c = H(0x321, 4 w +
+// 2) << 32 | H(0x321, 4 w + 3); v_i = H(0x322, 4 t + i). Step s, 32-bit unless said:
+//   k = T[(a ^ s) % 1024];  m = a k (64 bits);  a ^= hi(m);  b += lo(m)
+//   c += b << 32 | a;  c -= k                                      (64 bits)
+//   a ^= b << k % 32;  b ^= a >> (k >> 5) % 32;  a += signed(b) >> (k >> 10) % 32   (arithmetic)
+//   c = rotl64(c, (k >> 15) % 32 + 1)
+//   off = (k >> 20) % 16, wd = (k >> 24) % 16 + 1;  e = bits [off, off + wd) of a;  se = the
+//   same bits of b, sign-extended
+//   b += popcount(a) + 33 ctz(a) + 97 clz(b)                       (ctz(0) = clz(0) = 32)
+//   a ^= bitreverse(b);  a = a < b ? a + e : a - se
+//   b = max(b, k) - min(signed(a), signed(k));  a += |signed(a) - signed(b)|
+//   a ^= lo(c);  b ^= hi(c)
+//   v_{s & 3} = rotl32(v_{s & 3}, 7) + (a ^ l * 0x01000193);  v_{(s + 2) & 3} ^= b + l
+// and the signature is v_0..v_3.
+//
+// trans. g_i = H(0x331, 4 t + i). Step s: h = H(0x330, 256 s + t), carry = g_0 & 1 (which makes
+// the chain dependent); n = h % 32 - 16 + carry, neg = (h >> 5) & 1, k = (h >> 6) % 16 - 8,
+// k16 = (h >> 6) % 8 - 3, m = (h >> 10) % 4096, a = (h >> 22) % 128 - 64 + carry. The bit patterns
+// of these results are folded, in this order, for the operations in GM_LANESCAN_TRANS_OPS:
+//   g_0: v_exp_f32(n) = 2^n;  v_log_f32(2^n) = n;  v_rcp_f32(+-2^n) = +-2^-n;
+//        v_rsq_f32(4^k) = 2^-k;  v_sqrt_f32(m^2) = m
+//   g_1: v_sin_f32(a / 4), v_cos_f32(a / 4) (the operand is in turns): 0, 1, 0, -1 by a % 4
+//   g_2: v_rcp_f64(+-2^n), [v_sqrt_f64(4^k)], v_rsq_f64(4^k), each as lo ^ rotl32(hi, 16)
+//   g_3: v_rcp_f16(2^k), v_sqrt_f16(4^k16), v_rsq_f16(4^k16)
+// The host computes each by exponent arithmetic, without libm. A zero result of log, sqrt, sin and
+// cos is folded as 0: its sign is not part of the test. v_sqrt_f64 is not in the chain: on an
+// MI355X it returns 2^k (1 + 2^-26) at 4^k, inside its documented accuracy but not exact.
+//
+// f64. x = H(0x340, t) >> 6 (< 2^26), S = 0. Step s: h1 = H(0x341, 2 (256 s + t)), h2 = the next;
+// a = h1 % 2^16 - 2^15, b = h2 % 2^24 - 2^23, e = (h1 >> 16) % 4, c = (h1 >> 18) % 64 + 1,
+// d = h2 >> 24:
+//   p = fma(x, a, b);  S += p;  r = ldexp(p, e - 3) * c + d / 8;  fl = floor(r)
+//   x = fma(floor(ldexp(fl, -26)), -2^26, fl)   (= fl mod 2^26), then x = (double)(uint32_t)x
+//   g_0 = fold(g_0, W(p));  g_1 = fold(g_1, W(r));
+//   g_2 = fold(g_2, (x ^ (uint32_t)(8 (r - fl)) << 28) + (int32_t)ldexp(p, -12))
+// and g_3 = W(S), W(v) = lo ^ rotl32(hi, 16) of v's bits. |p| < 2^42, r is below 2^52 eighths, and
+// |S| <= 8 iters 2^42 < 2^53 for iters <= 255: every intermediate is an integer below 2^53 times a
+// power of two, and the host computes in int64_t.
+//
+// packed. Step s: h_q = H(0x350, 4 (256 s + t) + q), q = 0..3.
+//   v_pk_fma_f32:  acc_i += byte_i(h_0) * byte_{2 + i}(h_0), i = 0, 1 (signed bytes)
+//   A_i = (h_1 >> 6 i) % 64 - 32, B_i = (h_1 >> 12 + 6 i) % 64 - 32, C_i = (h_1 >> 24 + 4 i) % 16 - 8
+//   g_0 folds v_pk_fma_f16(A, B, C), then v_pk_add_f16(that, B), then v_pk_mul_f16(A, C)
+//   g_1 folds, on the halves of h_2 and h_3: v_pk_mul_lo_u16, v_pk_add_u16, v_pk_sub_i16,
+//       v_pk_max_i16, v_pk_min_u16
+//   sdot = v_dot4_i32_i8(h_2, h_3, sdot);  udot = v_dot4_u32_u8(h_2, h_3, udot)
+//   fdot = v_dot2_f32_f16(A, B, fdot);  bdot = v_dot2_f32_bf16(A, C, bdot)
+// and g_2 = bits(acc_0) + rotl32(bits(acc_1), 11), g_3 = sdot ^ rotl32(udot, 8) ^ bits(fdot) ^
+// rotl32(bits(bdot), 24). Every f16 value is an integer of magnitude <= 2048 and every sum is
+// exact in any order: 16 iters 2^14 < 2^24 bounds iters by 63, which is GM_LANESCAN_MAX_ITERS (the
+// static_asserts in gm_lanescan_ref.h hold every cap). A zero product of a negative factor is -0.
+//
+// Not covered: v_sqrt_f64 (above), v_cvt_scalef32_*, rounding, NaN, infinity and subnormal
+// behaviour, transcendental results at points that are not exact, the vector L1 and L2 caches,
+// the instruction cache, LDS atomics, clocks and thermals.
+//
+// The records, the injection, the per-CU entries and the result are the CU scan's, with `test`
+// and `tests_failed` holding GM_LANESCAN_* bits. Arguments and the up-front hipErrorInvalidValue
+// checks are those of the gm_probe_cuscan* counterparts, with 1 <= iters <= GM_LANESCAN_MAX_ITERS.
+int gm_probe_lanescan_expected(uint32_t test, uint64_t seed, uint32_t iters, uint32_t* out);
+// The xlane menu, menu[5 m + 0..4] = {kind, immediate, row_mask, bank_mask, bound_ctrl} of entry m
+// (kind 0: DPP with the immediate as dpp_ctrl; 1: ds_swizzle with it as offset; otherwise the
+// entry's own number, 34..42 as listed above), *n_menu entries (menu_cap must hold them), and the
+// GM_LANESCAN_OP_* mask of the operations in the trans chain. Host only, needs no GPU.
+int gm_probe_lanescan_lanes(uint32_t* menu, int menu_cap, int* n_menu, uint32_t* trans_ops);
+// One block, raw. Unlike its counterparts this one returns after the block has run: the scalar
+// test's table lives in a device buffer of the call's own.
+int gm_probe_lanescan_signature(uint32_t test, uint64_t seed, uint32_t iters, uint32_t* dev_out,
+                                uint32_t* dev_where, void* stream);
+int gm_probe_lanescan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed, int min_rounds,
+                      int max_rounds, const gm_cuscan_inject_t* inject, gm_cuscan_result_t* out,
+                      gm_cuscan_cu_t* cus, int cus_cap, int* n_cus);
+// numRegs and localSizeBytes of the scan kernel from hipFuncGetAttributes on the current device.
+// The register march is a register march only while *scratch_bytes is 0.
+int gm_probe_lanescan_kernel_info(int* num_regs, int* scratch_bytes);
 
 // ------------------------------------------------------------------ host link (PCIe) test
 // Moves checked bytes between pinned host memory and the GPU, in both directions, by the copy
