@@ -366,6 +366,15 @@ def probe() -> C.CDLL:
         lib.gm_probe_props.argtypes = [C.c_int, C.POINTER(ProbeProps)]
         lib.gm_probe_find_device.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
         lib.gm_probe_quick.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        lib.gm_probe_quick_expected.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.gm_probe_quick_verdict.argtypes = [C.POINTER(C.c_uint32), C.c_uint32,
+                                               C.POINTER(C.c_uint32)]
+        lib.gm_probe_quick_words.argtypes = [C.c_int, C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint32)]
+        lib.gm_probe_quick_flip.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+        lib.gm_probe_mfma_peak_values.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int,
+                                                  C.c_void_p, C.c_void_p]
         lib.gm_probe_hbm_copy.argtypes = [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_double)]
         lib.gm_probe_hbm_copy_variant.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int,
                                                   C.POINTER(C.c_double)]

@@ -48,13 +48,58 @@ def find_device(bdf: str) -> int:
     return d.value
 
 
-def quick(dev: int) -> float:
-    """Liveness kernel; returns launch→readback µs. Raises if the wave64 checks fail."""
+QUICK_WORDS = 66              # 64 lane words, the reduction sum (word 64), the ballot count (65)
+QUICK_BAD_LANES, QUICK_BAD_SUM, QUICK_BAD_BALLOT = 1, 2, 4
+_QUICK_CHECKS = ((QUICK_BAD_LANES, "lane words"), (QUICK_BAD_SUM, "reduction sum"),
+                 (QUICK_BAD_BALLOT, "ballot count"))
+
+
+def quick(dev: int, _flip: Optional[Tuple[int, int]] = None) -> float:
+    """Liveness kernel; returns launch→readback µs. Raises if the wave64 checks fail.
+    ``_flip=(word, mask)`` is the negative control: that one of the 66 words read back is XORed
+    with the nonzero 32-bit ``mask`` on the host before the verdict, so the call must raise."""
     ok, us = C.c_int(0), C.c_double(0)
-    _check(_native.probe().gm_probe_quick(dev, C.byref(ok), C.byref(us)), "quick probe")
+    if _flip is None:
+        _check(_native.probe().gm_probe_quick(dev, C.byref(ok), C.byref(us)), "quick probe")
+        if not ok.value:
+            raise ProbeError(f"device {dev}: liveness kernel produced wrong results")
+        return us.value
+    word, mask = _flip
+    for v in (word, mask):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < 1 << 32:
+            raise ProbeError(f"quick probe: flip {_flip!r} is not (word, mask) in 32 bits")
+    failed = C.c_uint32(0)
+    _check(_native.probe().gm_probe_quick_flip(dev, word, mask, C.byref(ok), C.byref(failed),
+                                               C.byref(us)), "quick probe")
     if not ok.value:
-        raise ProbeError(f"device {dev}: liveness kernel produced wrong results")
+        names = ", ".join(n for bit, n in _QUICK_CHECKS if failed.value & bit)
+        raise ProbeError(f"device {dev}: liveness kernel produced wrong results ({names})")
     return us.value
+
+
+def quick_expected(salt: int) -> List[int]:
+    """The 66 words the liveness kernel must produce for ``salt`` (host only; gm_probe.h)."""
+    words = (C.c_uint32 * QUICK_WORDS)()
+    _check(_native.probe().gm_probe_quick_expected(salt, words), "quick expected")
+    return list(words)
+
+
+def quick_verdict(words: Sequence[int], salt: int) -> int:
+    """The host verdict over 66 received words: 0 if healthy, else the QUICK_BAD_* bits of the
+    checks that failed (host only)."""
+    if len(words) != QUICK_WORDS:
+        raise ProbeError(f"quick verdict: {len(words)} words, not {QUICK_WORDS}")
+    failed = C.c_uint32(0)
+    _check(_native.probe().gm_probe_quick_verdict((C.c_uint32 * QUICK_WORDS)(*words), salt,
+                                                  C.byref(failed)), "quick verdict")
+    return failed.value
+
+
+def quick_words(dev: int) -> Tuple[List[int], int]:
+    """One run of the liveness kernel on ``dev``: (the 66 raw words read back, the salt used)."""
+    words, salt = (C.c_uint32 * QUICK_WORDS)(), C.c_uint32(0)
+    _check(_native.probe().gm_probe_quick_words(dev, words, C.byref(salt)), "quick words")
+    return list(words), salt.value
 
 
 def hbm_gbps(dev: int, nbytes: int = 1 << 30, iters: int = 10) -> float:
@@ -75,6 +120,32 @@ def mfma_tflops(dev: int, iters: int = 20000) -> float:
     t = C.c_double(0)
     _check(_native.probe().gm_probe_mfma_peak(dev, iters, C.byref(t)), "mfma peak")
     return t.value
+
+
+MFMA_PEAK_FLOATS = (64, 16, 32)    # accumulator floats per thread: chains × registers
+
+
+def mfma_peak_values(variant: int, iters: int, seed: float, blocks: int, out=None, stream=None):
+    """What MFMA peak kernel ``variant`` (0..2) computes: one launch of ``blocks`` blocks through
+    the timed driver's launch, every thread storing its accumulators after the loop. Returns an
+    fp32 tensor [blocks, 256, chains, registers] (4×16, 4×4, 8×4; operands and lane maps in
+    gm_probe.h). ``out``, if given, is a contiguous fp32 device tensor of exactly that many
+    elements; otherwise one is made on the current device. Waits for the kernel."""
+    import torch
+
+    if variant not in (0, 1, 2) or not isinstance(blocks, int) or blocks <= 0:
+        raise ProbeError(f"mfma_peak_values: variant {variant!r} or blocks {blocks!r}")
+    per = MFMA_PEAK_FLOATS[variant]
+    if out is None:
+        out = torch.empty(blocks * 256 * per, dtype=torch.float32, device="cuda")
+    elif out.dtype != torch.float32 or out.numel() != blocks * 256 * per:
+        raise ProbeError(f"mfma_peak_values: out must hold {blocks * 256 * per} fp32")
+    _dev_bytes(out, "mfma_peak_values")
+    with torch.cuda.device(out.device):
+        _check(_native.probe().gm_probe_mfma_peak_values(variant, iters, seed, blocks,
+                                                         out.data_ptr(), _stream_of(out, stream)),
+               "mfma peak values")
+    return out.view(blocks, 256, 4 if variant < 2 else 8, 16 if variant == 0 else 4)
 
 
 def gemm_check(dev: int, m: int = 256, n: int = 256, k: int = 256) -> Dict[str, float]:
@@ -99,8 +170,14 @@ def gemm_bf16(a, b, out=None, stream=None):
     k2, n = b.shape
     if k != k2 or m % 64 or n % 64 or k % 32:
         raise ProbeError(f"unsupported shape A{tuple(a.shape)} B{tuple(b.shape)}")
+    if a.device != b.device:
+        raise ProbeError(f"gemm_bf16: A on {a.device}, B on {b.device}")
     if out is None:
         out = torch.empty((m, n), dtype=torch.float32, device=a.device)
+    elif (not isinstance(out, torch.Tensor) or out.shape != (m, n) or out.dtype != torch.float32
+          or not out.is_contiguous() or out.device != a.device):
+        raise ProbeError(f"gemm_bf16: out must be a contiguous fp32 [{m},{n}] tensor on "
+                         f"{a.device}")
     s = stream if stream is not None else torch.cuda.current_stream(a.device)
     with torch.cuda.device(a.device):
         _check(_native.probe().gm_probe_gemm_bf16(a.data_ptr(), b.data_ptr(), out.data_ptr(),

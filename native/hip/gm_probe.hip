@@ -20,21 +20,22 @@
 #include <vector>
 
 #include "gm_probe_common.h"
+#include "gm_quick_ref.h"
 
 namespace {
 
 // ------------------------------------------------------------------ liveness
 __global__ __launch_bounds__(64) void k_quick(uint32_t* out, uint32_t salt) {
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t v = lane * 2654435761u ^ salt;
+  const uint32_t v = gm_quick_lane_value(lane, salt);
   out[lane] = v;
   // wave-wide reduction through 64-lane shuffles: the checksum lands in lane 0
   uint32_t s = v;
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
   const unsigned long long ballot = __ballot(1);
   if (lane == 0) {
-    out[64] = s;
-    out[65] = (uint32_t)__popcll(ballot);  // 64 on a wave64 machine
+    out[GM_QUICK_SUM_WORD] = s;
+    out[GM_QUICK_BALLOT_WORD] = (uint32_t)__popcll(ballot);  // 64 on a wave64 machine
   }
 }
 
@@ -153,7 +154,21 @@ __global__ __launch_bounds__(256) void k_fill(float4* dst, size_t n, float v) {
 // ------------------------------------------------------------------ MFMA peak
 // 4 independent 32x32 accumulators per wave hide the dependent-MFMA latency; operands stay in
 // registers so the loop measures the matrix pipe alone.
-__global__ __launch_bounds__(256) void k_mfma_peak(float* out, int iters, float seed) {
+// `vals`, when not null, receives every accumulator register after the loop as
+// vals[block][thread][chain][register] (gm_probe_mfma_peak_values); the timed drivers pass null
+// and launch the same kernels, so the values that are checked come from the loop that is timed.
+template <int kChains, typename Acc>
+__device__ __forceinline__ void store_chains(float* vals, const Acc (&c)[kChains]) {
+  constexpr int kRegs = sizeof(Acc) / sizeof(float);
+  float* p = vals + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (kChains * kRegs);
+#pragma unroll
+  for (int ch = 0; ch < kChains; ++ch)
+#pragma unroll
+    for (int r = 0; r < kRegs; ++r) p[ch * kRegs + r] = c[ch][r];
+}
+
+__global__ __launch_bounds__(256) void k_mfma_peak(float* out, int iters, float seed,
+                                                   float* vals) {
   bf16x8 a, b;
   for (int j = 0; j < 8; ++j) {
     a[j] = (__bf16)(seed * (float)(threadIdx.x + j));
@@ -170,6 +185,10 @@ __global__ __launch_bounds__(256) void k_mfma_peak(float* out, int iters, float 
   for (int j = 0; j < 16; ++j) s += c0[j] + c1[j] + c2[j] + c3[j];
   if (s == 1234.5678f) out[0] = s;  // keeps the loop alive without a store per thread
   if (threadIdx.x == 0 && blockIdx.x == 0) out[1] = s;
+  if (vals) {
+    const f32x16 c[4] = {c0, c1, c2, c3};
+    store_chains(vals, c);
+  }
 }
 
 // 16x16x32 form: ≈1.15× the FLOP/s of 32x32x16 under DVFS on random data (MI355X_MICROARCH
@@ -180,8 +199,17 @@ __global__ __launch_bounds__(256) void k_mfma_peak(float* out, int iters, float 
 // are needed inside the loop.
 #define GM_MFMA16(c, x, y) \
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(x), "v"(y))
+// After the loop they are: the compiler does not know that the statements above are MFMAs, so it
+// pads nothing between the last one and its own first read of an accumulator (for the builtin it
+// does). An 8-pass MFMA's result needs 12 wait states before anything but the next MFMA of its
+// chain touches it. This statement goes after the loop: a volatile asm stays behind the MFMAs,
+// and the "+a" operands keep every reader of those accumulators behind it. It costs 12 states
+// per launch; the loop is untouched.
+#define GM_MFMA16_DRAIN4(c0, c1, c2, c3) \
+  asm volatile("s_nop 11" : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3))
 
-__global__ __launch_bounds__(256) void k_mfma_peak16(float* out, int iters, float seed) {
+__global__ __launch_bounds__(256) void k_mfma_peak16(float* out, int iters, float seed,
+                                                     float* vals) {
   bf16x8 a, b;
   for (int j = 0; j < 8; ++j) {
     a[j] = (__bf16)(seed * (float)(threadIdx.x * 7 + j));
@@ -194,14 +222,20 @@ __global__ __launch_bounds__(256) void k_mfma_peak16(float* out, int iters, floa
     GM_MFMA16(c2, a, a);
     GM_MFMA16(c3, b, b);
   }
+  GM_MFMA16_DRAIN4(c0, c1, c2, c3);
   float s = 0.f;
   for (int j = 0; j < 4; ++j) s += c0[j] + c1[j] + c2[j] + c3[j];
   if (s == 1234.5678f) out[0] = s;
   if (threadIdx.x == 0 && blockIdx.x == 0) out[1] = s;
+  if (vals) {
+    const f32x4 c[4] = {c0, c1, c2, c3};
+    store_chains(vals, c);
+  }
 }
 
 // 8 independent 16x16x32 chains: twice the MFMAs in flight per wave of k_mfma_peak16.
-__global__ __launch_bounds__(256) void k_mfma_peak16x8(float* out, int iters, float seed) {
+__global__ __launch_bounds__(256) void k_mfma_peak16x8(float* out, int iters, float seed,
+                                                       float* vals) {
   bf16x8 a, b;
   for (int j = 0; j < 8; ++j) {
     a[j] = (__bf16)(seed * (float)(threadIdx.x * 7 + j));
@@ -218,10 +252,16 @@ __global__ __launch_bounds__(256) void k_mfma_peak16x8(float* out, int iters, fl
     GM_MFMA16(c6, a, a);
     GM_MFMA16(c7, b, b);
   }
+  GM_MFMA16_DRAIN4(c0, c1, c2, c3);
+  GM_MFMA16_DRAIN4(c4, c5, c6, c7);
   float s = 0.f;
   for (int j = 0; j < 4; ++j) s += c0[j] + c1[j] + c2[j] + c3[j] + c4[j] + c5[j] + c6[j] + c7[j];
   if (s == 1234.5678f) out[0] = s;
   if (threadIdx.x == 0 && blockIdx.x == 0) out[1] = s;
+  if (vals) {
+    const f32x4 c[8] = {c0, c1, c2, c3, c4, c5, c6, c7};
+    store_chains(vals, c);
+  }
 }
 
 // ------------------------------------------------------------------ MFMA bf16 GEMM
@@ -336,6 +376,38 @@ int launch_read(const float4* src, uint32_t* sink, size_t n, int blocks, hipStre
 
 bool aligned16(const void* p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
 
+// One launch of an MFMA peak kernel: the timed driver (vals null) and gm_probe_mfma_peak_values
+// both come through here. `out` holds 2 floats.
+bool mfma_variant_ok(int variant) { return variant >= 0 && variant <= 2; }
+
+int launch_mfma_peak(int variant, int blocks, float* out, int iters, float seed, float* vals,
+                     hipStream_t s) {
+  if (blocks <= 0 || iters <= 0) return (int)hipErrorInvalidValue;
+  const dim3 grid(blocks), block(256);
+  switch (variant) {
+    case 0: hipLaunchKernelGGL(k_mfma_peak, grid, block, 0, s, out, iters, seed, vals); break;
+    case 1: hipLaunchKernelGGL(k_mfma_peak16, grid, block, 0, s, out, iters, seed, vals); break;
+    case 2: hipLaunchKernelGGL(k_mfma_peak16x8, grid, block, 0, s, out, iters, seed, vals); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
+}
+
+// The liveness kernel on `dev`'s cached scratch: 66 words in s->quick_host afterwards.
+int run_quick(int dev, Scratch** sp, uint32_t* salt, double* elapsed_us) {
+  Scratch* s = scratch(dev);
+  if (!s) return (int)hipErrorOutOfMemory;
+  const double t0 = now_s();
+  *salt = gm_quick_salt(dev);
+  hipLaunchKernelGGL(k_quick, dim3(1), dim3(64), 0, 0, s->quick, *salt);
+  GM_CHECK(hipGetLastError());
+  GM_CHECK(hipMemcpy(s->quick_host, s->quick, GM_QUICK_WORDS * sizeof(uint32_t),
+                     hipMemcpyDeviceToHost));
+  *elapsed_us = (now_s() - t0) * 1e6;
+  *sp = s;
+  return 0;
+}
+
 uint16_t f2bf(float f) {
   uint32_t u;
   memcpy(&u, &f, 4);
@@ -390,24 +462,50 @@ int gm_probe_quick(int dev, int* ok, double* elapsed_us) {
   *ok = 0;
   DeviceGuard g(dev);
   if (!g.ok) return (int)hipErrorInvalidDevice;
-  Scratch* s = scratch(dev);
-  if (!s) return (int)hipErrorOutOfMemory;
-  const double t0 = now_s();
-  const uint32_t salt = 0x9e3779b9u ^ (uint32_t)dev;
-  hipLaunchKernelGGL(k_quick, dim3(1), dim3(64), 0, 0, s->quick, salt);
-  GM_CHECK(hipGetLastError());
-  GM_CHECK(hipMemcpy(s->quick_host, s->quick, 66 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  const double t1 = now_s();
-  uint32_t sum = 0;
-  bool good = true;
-  for (uint32_t l = 0; l < 64; ++l) {
-    const uint32_t v = l * 2654435761u ^ salt;
-    good &= s->quick_host[l] == v;
-    sum += v;
-  }
-  good &= s->quick_host[64] == sum && s->quick_host[65] == 64;
-  *ok = good ? 1 : 0;
-  *elapsed_us = (t1 - t0) * 1e6;
+  Scratch* s = nullptr;
+  uint32_t salt = 0;
+  if (int e = run_quick(dev, &s, &salt, elapsed_us)) return e;
+  *ok = gm_quick_verdict(s->quick_host, salt) == 0 ? 1 : 0;
+  return 0;
+}
+
+int gm_probe_quick_flip(int dev, uint32_t word, uint32_t mask, int* ok, uint32_t* failed,
+                        double* elapsed_us) {
+  if (!ok || !failed || !elapsed_us) return (int)hipErrorInvalidValue;
+  *ok = 0;
+  *failed = 0;
+  if (word >= GM_QUICK_WORDS || mask == 0) return (int)hipErrorInvalidValue;
+  DeviceGuard g(dev);
+  if (!g.ok) return (int)hipErrorInvalidDevice;
+  Scratch* s = nullptr;
+  uint32_t salt = 0;
+  if (int e = run_quick(dev, &s, &salt, elapsed_us)) return e;
+  s->quick_host[word] ^= mask;  // the next run copies all 66 words back over it
+  *failed = gm_quick_verdict(s->quick_host, salt);
+  *ok = *failed == 0 ? 1 : 0;
+  return 0;
+}
+
+int gm_probe_quick_words(int dev, uint32_t* words, uint32_t* salt) {
+  if (!words || !salt) return (int)hipErrorInvalidValue;
+  DeviceGuard g(dev);
+  if (!g.ok) return (int)hipErrorInvalidDevice;
+  Scratch* s = nullptr;
+  double us = 0;
+  if (int e = run_quick(dev, &s, salt, &us)) return e;
+  memcpy(words, s->quick_host, GM_QUICK_WORDS * sizeof(uint32_t));
+  return 0;
+}
+
+int gm_probe_quick_expected(uint32_t salt, uint32_t* words) {
+  if (!words) return (int)hipErrorInvalidValue;
+  gm_quick_expected(salt, words);
+  return 0;
+}
+
+int gm_probe_quick_verdict(const uint32_t* words, uint32_t salt, uint32_t* failed) {
+  if (!words || !failed) return (int)hipErrorInvalidValue;
+  *failed = gm_quick_verdict(words, salt);
   return 0;
 }
 
@@ -509,13 +607,10 @@ int gm_probe_mfma_peak_variant(int dev, int variant, int iters, int blocks_per_c
   float* out = nullptr;
   GM_CHECK(hipMalloc(&out, 2 * sizeof(float)));
   const int blocks = p.multiProcessorCount * blocks_per_cu;
+  // any variant but 1 and 2 times the 32x32x16 kernel, as it always has
+  const int kernel = mfma_variant_ok(variant) ? variant : 0;
   auto launch = [&](int it) {
-    if (variant == 1)
-      hipLaunchKernelGGL(k_mfma_peak16, dim3(blocks), dim3(256), 0, 0, out, it, 1e-3f);
-    else if (variant == 2)
-      hipLaunchKernelGGL(k_mfma_peak16x8, dim3(blocks), dim3(256), 0, 0, out, it, 1e-3f);
-    else
-      hipLaunchKernelGGL(k_mfma_peak, dim3(blocks), dim3(256), 0, 0, out, it, 1e-3f);
+    (void)launch_mfma_peak(kernel, blocks, out, it, 1e-3f, nullptr, nullptr);
   };
   hipEvent_t a, b;
   (void)hipEventCreate(&a);
@@ -548,6 +643,18 @@ int gm_probe_hbm_copy(int dev, uint64_t bytes, int iters, double* gbps) {
 // (≈98 % of the 2.5 PF/s dense bf16 peak) vs 2.0-2.16 PF/s for 32x32x16 × 4 chains.
 int gm_probe_mfma_peak(int dev, int iters, double* tflops) {
   return gm_probe_mfma_peak_variant(dev, 2, iters, 8, tflops);
+}
+
+int gm_probe_mfma_peak_values(int variant, int iters, float seed, int blocks, float* dev_out,
+                              void* stream) {
+  if (!mfma_variant_ok(variant) || iters <= 0 || blocks <= 0 || !aligned16(dev_out))
+    return (int)hipErrorInvalidValue;
+  DevBuf out;  // the two floats the timed driver's `out` holds
+  GM_CHECK(out.alloc(2 * sizeof(float)));
+  int e = launch_mfma_peak(variant, blocks, (float*)out.p, iters, seed, dev_out,
+                           (hipStream_t)stream);
+  if (!e) e = (int)hipStreamSynchronize((hipStream_t)stream);  // `out` is freed on return
+  return e;
 }
 
 int gm_probe_gemm_bf16(const void* A, const void* B, float* C, int M, int N, int K,

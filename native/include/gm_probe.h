@@ -31,6 +31,26 @@ int gm_probe_find_device(const char* bdf, int* dev);
 // Liveness: launches one wave64 kernel that writes lane ids and a checksum; verifies on host.
 // *elapsed_us = launch→readback wall time.
 int gm_probe_quick(int dev, int* ok, double* elapsed_us);
+// What the liveness kernel writes and how the host judges it (one implementation, shared with the
+// kernel: gm_quick_ref.h). With salt = 0x9e3779b9 ^ dev, all arithmetic in uint32:
+//   word l, l = 0..63:  l · 2654435761 ^ salt        (lane l's own store)
+//   word 64:            the sum of words 0..63        (64-lane shuffle reduction, lane 0 stores)
+//   word 65:            64                            (popcount of the wave's ballot)
+// The verdict makes three independent checks against that table and reports the ones that failed
+// as bits: 1 a lane word, 2 the sum word, 4 the ballot word (GM_QUICK_BAD_*); 0 = healthy.
+// Host only, no HIP call: the 66 expected words for `salt`; the verdict over a caller's 66 words.
+// A null pointer is hipErrorInvalidValue.
+int gm_probe_quick_expected(uint32_t salt, uint32_t* words);
+int gm_probe_quick_verdict(const uint32_t* words, uint32_t salt, uint32_t* failed);
+// Runs the kernel on `dev` exactly as gm_probe_quick does and returns the 66 raw words read back
+// and the salt used, without judging them.
+int gm_probe_quick_words(int dev, uint32_t* words, uint32_t* salt);
+// gm_probe_quick's negative control: the same run, but word `word` (< 66) of the host copy is
+// XORed with the nonzero `mask` before the verdict, so *ok must come out 0 and *failed must name
+// that word's check. The device buffer and later runs are not affected. word >= 66, mask == 0 or
+// a null pointer: hipErrorInvalidValue before any HIP call.
+int gm_probe_quick_flip(int dev, uint32_t word, uint32_t mask, int* ok, uint32_t* failed,
+                        double* elapsed_us);
 // HBM3E stream: float4 copy of `bytes` for `iters`; *gbps = (read+write) bytes / time. The
 // default variant is 2. Both timed drivers round `bytes` down to a multiple of 16 and return the
 // HIP error of a failed launch instead of a rate.
@@ -62,6 +82,24 @@ int gm_probe_mfma_peak_variant(int dev, int variant, int iters, int blocks_per_c
                                double* tflops);
 // MFMA bf16 register-resident peak (best measured form: 16x16x32 × 8 chains); *tflops dense.
 int gm_probe_mfma_peak(int dev, int iters, double* tflops);
+// What those kernels compute: exactly one launch of peak kernel `variant` (0..2), through the
+// launch the timed driver uses, with `blocks` blocks of 256 threads on the current device. The
+// timed driver passes the kernel a null value pointer; here every thread stores every accumulator
+// register after the loop: dev_out[block][thread][chain][register], chains × registers being
+// 4 × 16 (variant 0), 4 × 4 (variant 1) and 8 × 4 (variant 2) floats per thread, so dev_out holds
+// blocks × 256 × 64, 16 or 32 floats. Each wave of 64 threads computes, per chain, `iters`
+// accumulations of one MFMA tile product C += A·B. With t = threadIdx.x, l = t & 63 and
+// n_a(j), n_b(j) the integers below, lane l holds a[j] = bf16(seed · n_a(j)) and
+// b[j] = bf16(seed · n_b(j)), j = 0..7 (product in fp32, then rounded to nearest even):
+//   variant 0:    n_a = t + j,   n_b = j + 1;   A[l&31][8(l>>5)+j], B[8(l>>5)+j][l&31] (K = 16),
+//                 register i of lane l is C[(i&3) + 8(i>>2) + 4(l>>5)][l&31]
+//   variant 1, 2: n_a = 7t + j,  n_b = 3j + 1 + blockIdx.x;  A[l&15][8(l>>4)+j],
+//                 B[8(l>>4)+j][l&15] (K = 32), register i of lane l is C[4(l>>4) + i][l&15]
+// The chains take (A, B) from the lanes' (a, b), (b, a), (a, a), (b, b) in that order; variant 2
+// repeats the four. Waits for the kernel. A variant outside 0..2, iters <= 0, blocks <= 0 or a
+// dev_out that is null or not 16-byte aligned: hipErrorInvalidValue before any HIP call.
+int gm_probe_mfma_peak_values(int variant, int iters, float seed, int blocks, float* dev_out,
+                              void* stream);
 // C[M,N] (fp32) = A[M,K] (bf16, row-major) · B[K,N] (bf16, row-major) on MFMA.
 // Requires M%64 == 0, N%64 == 0, K%32 == 0 (checked). Device pointers; stream may be NULL.
 int gm_probe_gemm_bf16(const void* A, const void* B, float* C, int M, int N, int K, void* stream);

@@ -1,10 +1,12 @@
 """Host side of the caller-owned-buffer probe entry points (gpumounter_amd/ops/probe.py,
 native/include/gm_probe.h): argument validation before any HIP call, the ``--burn-in-flip``
-parser and its plumbing into ``probe`` and ``doctor``. No GPU needed; what the kernels do to data
+parser and its plumbing into ``probe`` and ``doctor``, and the liveness probe's expected table
+and verdict (native/include/gm_quick_ref.h). No GPU needed; what the kernels do to data
 is covered by tests/test_probe_data_gpu.py."""
 import ctypes as C
 import inspect
 
+import numpy as np
 import pytest
 import torch
 
@@ -69,6 +71,132 @@ def test_wrappers_validate_their_tensors():
                  lambda: probe.fill_bf16([0] * 8, 1), lambda: probe.count_diff([0] * 16, z)):
         with pytest.raises(probe.ProbeError):
             call()
+
+
+# ------------------------------------------------------------------ liveness probe verdict
+QUICK_SALTS = (0, 1, 0x9E3779B9, 0x9E3779B9 ^ 3, 0xFFFFFFFF, 0x80000001)
+
+
+def _quick_reference(salt: int) -> np.ndarray:
+    """gm_probe.h's formula in numpy: uint64 arithmetic reduced mod 2^32 at the end."""
+    lanes = ((np.arange(64, dtype=np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) \
+        ^ np.uint64(salt)
+    return np.concatenate([lanes, [lanes.sum() & np.uint64(0xFFFFFFFF)], [64]]).astype(np.uint32)
+
+
+def _check_of(word: int) -> int:
+    return (probe.QUICK_BAD_LANES if word < 64 else
+            probe.QUICK_BAD_SUM if word == 64 else probe.QUICK_BAD_BALLOT)
+
+
+@pytest.mark.parametrize("salt", QUICK_SALTS)
+def test_quick_expected_table_is_the_documented_formula(salt):
+    want = _quick_reference(salt)
+    got = probe.quick_expected(salt)
+    assert len(got) == probe.QUICK_WORDS == 66
+    np.testing.assert_array_equal(np.array(got, dtype=np.uint32), want)
+    assert probe.quick_verdict(got, salt) == 0
+    assert probe.quick_verdict([int(w) for w in want], salt) == 0
+
+
+@pytest.mark.parametrize("salt", QUICK_SALTS[:3])
+def test_quick_verdict_fails_every_single_bit_flip_and_names_the_check(salt):
+    lib = _native.probe()
+    want = probe.quick_expected(salt)
+    buf, failed = (C.c_uint32 * 66)(*want), C.c_uint32(0)
+    for word in range(66):
+        for bit in range(32):
+            buf[word] = want[word] ^ (1 << bit)
+            failed.value = 0
+            assert lib.gm_probe_quick_verdict(buf, salt, C.byref(failed)) == 0
+            assert failed.value == _check_of(word), (word, bit, failed.value)
+        buf[word] = want[word]
+    assert lib.gm_probe_quick_verdict(buf, salt, C.byref(failed)) == 0 and failed.value == 0
+
+
+def test_quick_verdict_fails_a_wave32_ballot_and_another_salts_table():
+    salt = 0x9E3779B9
+    want = probe.quick_expected(salt)
+    assert probe.quick_verdict(want[:65] + [32], salt) == probe.QUICK_BAD_BALLOT
+    assert probe.quick_verdict(want[:65] + [0], salt) == probe.QUICK_BAD_BALLOT
+    # a sum that agrees with wrong lane words is still wrong lane words, and a right sum over
+    # them is a wrong sum only if it differs from the table's
+    other = probe.quick_expected(salt ^ 1)          # device 1's table judged as device 0's
+    assert other[:64] != want[:64]
+    assert probe.quick_verdict(other, salt) & probe.QUICK_BAD_LANES
+    assert probe.quick_verdict(other, salt ^ 1) == 0
+    for s2 in (0, 0x12345678, salt ^ 0x80000000):
+        o = probe.quick_expected(s2)
+        bad = probe.quick_verdict(o, salt)
+        assert bad & probe.QUICK_BAD_LANES and not bad & probe.QUICK_BAD_BALLOT
+        assert bool(bad & probe.QUICK_BAD_SUM) == (o[64] != want[64])
+    # lane 63 alone, and the three at once
+    assert probe.quick_verdict(want[:63] + [want[63] ^ 1] + want[64:], salt) \
+        == probe.QUICK_BAD_LANES
+    assert probe.quick_verdict([w ^ 0x100 for w in want], salt) == 7
+    with pytest.raises(probe.ProbeError):
+        probe.quick_verdict(want[:65], salt)
+
+
+def test_quick_entry_points_refuse_before_any_hip_call():
+    """hipErrorInvalidValue (1) with no device selected: a HIP call would have failed otherwise."""
+    lib = _native.probe()
+    ok, failed, us = C.c_int(7), C.c_uint32(7), C.c_double(0)
+    out = (C.byref(ok), C.byref(failed), C.byref(us))
+    for word, mask in ((66, 1), (67, 0x8000), (0xFFFFFFFF, 1), (0, 0), (65, 0)):
+        assert lib.gm_probe_quick_flip(0, word, mask, *out) == 1, (word, mask)
+        assert ok.value == 0 and failed.value == 0
+        with pytest.raises(probe.ProbeError, match="hip error 1 "):
+            probe.quick(0, _flip=(word, mask))
+    assert lib.gm_probe_quick_flip(0, 0, 1, None, C.byref(failed), C.byref(us)) == 1
+    for flip in ((-1, 1), (0, 1 << 32), (0.0, 1), (0, True)):
+        with pytest.raises(probe.ProbeError, match="flip"):
+            probe.quick(0, _flip=flip)
+    buf = (C.c_uint32 * 66)()
+    assert lib.gm_probe_quick_expected(0, None) == 1
+    assert lib.gm_probe_quick_verdict(None, 0, C.byref(failed)) == 1
+    assert lib.gm_probe_quick_verdict(buf, 0, None) == 1
+    assert lib.gm_probe_quick_words(0, None, C.byref(failed)) == 1
+    assert lib.gm_probe_quick_words(0, buf, None) == 1
+    assert inspect.signature(probe.quick).parameters["_flip"].default is None
+
+
+# ------------------------------------------------------------------ MFMA peak values, 64² GEMM
+def test_mfma_peak_values_refuses_before_any_hip_call():
+    lib = _native.probe()
+    for variant, iters, blocks, ptr in ((3, 1, 1, P), (-1, 1, 1, P), (0, 0, 1, P), (1, -5, 1, P),
+                                        (2, 1, 0, P), (2, 1, -1, P), (0, 1, 1, None),
+                                        (0, 1, 1, C.c_void_p(4096 + 4)),
+                                        (1, 1, 1, C.c_void_p(4096 + 8))):
+        assert lib.gm_probe_mfma_peak_values(variant, iters, 1.0, blocks, ptr, None) == 1
+    cpu = torch.zeros(3 * 256 * 16, dtype=torch.float32)
+    for call in (lambda: probe.mfma_peak_values(3, 1, 1.0, 3),
+                 lambda: probe.mfma_peak_values(1, 1, 1.0, 0),
+                 lambda: probe.mfma_peak_values(1, 1, 1.0, 3, out=cpu),                 # device
+                 lambda: probe.mfma_peak_values(0, 1, 1.0, 3, out=cpu),                 # size
+                 lambda: probe.mfma_peak_values(1, 1, 1.0, 3, out=cpu.to(torch.int32))):
+        with pytest.raises(probe.ProbeError):
+            call()
+
+
+def test_gemm_bf16_validates_out_before_any_hip_call():
+    """Operands on the CPU: anything but the refusal would need a device."""
+    bf = torch.bfloat16
+    a, b = torch.zeros(64, 32, dtype=bf), torch.zeros(32, 128, dtype=bf)
+    for out in (torch.zeros(64, 128, dtype=bf),                      # half the bytes the kernel writes
+                torch.zeros(64, 128, dtype=torch.float64),
+                torch.zeros(64, 64, dtype=torch.float32),            # undersized
+                torch.zeros(128, 64, dtype=torch.float32),           # transposed shape
+                torch.zeros(64 * 128, dtype=torch.float32),          # right size, wrong rank
+                torch.zeros(128, 64, dtype=torch.float32).t(),       # right shape, not contiguous
+                torch.zeros(64, 256, dtype=torch.float32)[:, ::2],
+                torch.empty(64, 128, dtype=torch.float32, device="meta"),   # another device
+                [0.0] * (64 * 128)):
+        with pytest.raises(probe.ProbeError, match="out must be"):
+            probe.gemm_bf16(a, b, out=out)
+    with pytest.raises(probe.ProbeError, match="A on"):
+        probe.gemm_bf16(a, torch.empty(32, 128, dtype=bf, device="meta"))
+    assert list(inspect.signature(probe.gemm_bf16).parameters) == ["a", "b", "out", "stream"]
 
 
 def test_parse_burn_in_flip():

@@ -45,6 +45,234 @@ def _rand_i32(n: int, seed: int):
                          generator=g).to(torch.int32)
 
 
+# ------------------------------------------------------------------ liveness probe
+def test_quick_raw_words_are_the_expected_table():
+    words, salt = probe.quick_words(0)
+    assert salt == 0x9E3779B9                       # device 0
+    want = probe.quick_expected(salt)
+    bad = [(i, hex(g), hex(w)) for i, (g, w) in enumerate(zip(words, want)) if g != w]
+    assert not bad, bad
+    assert words[65] == 64 and probe.quick_verdict(words, salt) == 0
+
+
+def test_quick_negative_control_fails_each_check_and_leaves_nothing_behind():
+    assert probe.quick(0) < 1e6
+    for flip, name in (((0, 0x1), "lane words"), ((63, 0x80000000), "lane words"),
+                       ((37, 0xFFFFFFFF), "lane words"), ((64, 0x1), "reduction sum"),
+                       ((64, 0x80000000), "reduction sum"), ((65, 0x40), "ballot count"),
+                       ((65, 0x60), "ballot count")):        # 64 ^ 0x60 = 32: a wave32 answer
+        with pytest.raises(probe.ProbeError, match=rf"wrong results \({name}\)"):
+            probe.quick(0, _flip=flip)
+        # the flip touched the host copy of that run only: the cached scratch serves a clean run
+        assert probe.quick(0) < 1e6
+        assert probe.quick_words(0)[0] == probe.quick_expected(0x9E3779B9)
+    for flip in ((66, 1), (0, 0)):
+        with pytest.raises(probe.ProbeError, match="hip error 1 "):
+            probe.quick(0, _flip=flip)
+    assert probe.quick(0) < 1e6
+
+
+# ------------------------------------------------------------------ MFMA peak kernels' values
+# The reference is written from the kernel source (native/hip/gm_probe.hip) and the lane maps in
+# gm_probe.h: per wave and chain one tile product, accumulated `iters` times.
+PEAK_BLOCKS = 3                                  # blockIdx enters b of the 16x16x32 kernels
+PEAK_GUARD, PEAK_SENTINEL = 1024, -12345.0       # floats on each side of the output
+PEAK_CHAINS = ("ab", "ba", "aa", "bb")
+_peak_cache = {}
+
+
+def _bf16_rne(x: np.ndarray) -> np.ndarray:
+    """float32 → bf16 (round to nearest even) → the value as float64."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    bits = (u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)
+    return (bits << np.uint32(16)).view(np.float32).astype(np.float64)
+
+
+def _peak_lane_operands(variant: int, block: int, seed: float):
+    """a[t][j], b[t][j] of the 256 threads of one block, as the kernels form them."""
+    t = np.arange(256)[:, None]
+    j = np.arange(8)[None, :]
+    if variant == 0:
+        na, nb = t + j, np.broadcast_to(j + 1, (256, 8))
+    else:
+        na, nb = t * 7 + j, np.broadcast_to(j * 3 + 1 + block, (256, 8))
+    s = np.float32(seed)
+    return _bf16_rne(s * na.astype(np.float32)), _bf16_rne(s * nb.astype(np.float32))
+
+
+def _peak_terms(variant: int, seed: float):
+    """For one iteration: terms[block, thread, chain, register, k], the K products a·b that the
+    register's output element sums (float64, exact: two bf16 factors)."""
+    key = (variant, float(np.float32(seed)))
+    if key in _peak_cache:
+        return _peak_cache[key]
+    rows, shift, regs = (32, 5, 16) if variant == 0 else (16, 4, 4)
+    kdim = 8 * (64 >> shift)
+    nchains = 8 if variant == 2 else 4
+    lane = np.arange(64)
+    out = np.zeros((PEAK_BLOCKS, 256, nchains, regs, kdim))
+    for blk in range(PEAK_BLOCKS):
+        a, b = _peak_lane_operands(variant, blk, seed)
+        for w in range(4):
+            ops = {"a": a[64 * w:64 * w + 64], "b": b[64 * w:64 * w + 64]}
+            for ch in range(nchains):
+                x, y = (ops[c] for c in PEAK_CHAINS[ch % 4])
+                A, B = np.zeros((rows, kdim)), np.zeros((kdim, rows))
+                for j in range(8):
+                    A[lane & (rows - 1), 8 * (lane >> shift) + j] = x[:, j]
+                    B[8 * (lane >> shift) + j, lane & (rows - 1)] = y[:, j]
+                terms = A[:, :, None] * B[None, :, :]             # [row, k, col]
+                for i in range(regs):
+                    row = ((i & 3) + 8 * (i >> 2) + 4 * (lane >> 5) if variant == 0
+                           else 4 * (lane >> 4) + i)
+                    out[blk, 64 * w + lane, ch, i, :] = terms[row, :, lane & (rows - 1)]
+    _peak_cache[key] = out
+    return out
+
+
+def _peak_run(variant: int, iters: int, seed: float) -> np.ndarray:
+    """One values launch between sentinel guards; asserts the guards, returns the values."""
+    per = probe.MFMA_PEAK_FLOATS[variant]
+    n = PEAK_BLOCKS * 256 * per
+    big = torch.full((n + 2 * PEAK_GUARD,), PEAK_SENTINEL, dtype=torch.float32, device=DEV)
+    got = probe.mfma_peak_values(variant, iters, seed, PEAK_BLOCKS,
+                                 out=big[PEAK_GUARD:PEAK_GUARD + n])
+    assert got.data_ptr() == big.data_ptr() + 4 * PEAK_GUARD
+    assert tuple(got.shape) == (PEAK_BLOCKS, 256, per // (16 if variant == 0 else 4),
+                                16 if variant == 0 else 4)
+    host = big.cpu().numpy()
+    assert (host[:PEAK_GUARD] == PEAK_SENTINEL).all(), "guard below the output overwritten"
+    assert (host[PEAK_GUARD + n:] == PEAK_SENTINEL).all(), "guard above the output overwritten"
+    return host[PEAK_GUARD:PEAK_GUARD + n].reshape(got.shape)
+
+
+def _assert_peak_exact(variant: int, iters: int):
+    terms = _peak_terms(variant, 1.0)
+    ints = terms.astype(np.int64)
+    assert (ints == terms).all()                                   # seed 1.0: integer terms
+    # exact in any accumulation order: every partial sum is a multiple of the lowest set bit
+    # among the element's terms and smaller than 2^24 of them
+    low = np.where(ints != 0, ints & -ints, np.int64(1) << 62).min(axis=-1).astype(np.float64)
+    assert (iters * np.abs(ints).sum(axis=-1) / low < 1 << 24).all(), \
+        f"variant {variant}: iters {iters} is not exact in fp32"
+    ref = (iters * terms.sum(axis=-1)).astype(np.float32)
+    assert (ref.astype(np.float64) == iters * terms.sum(axis=-1)).all()
+    got = _peak_run(variant, iters, 1.0)
+    wrong = got.view(np.uint32) != ref.view(np.uint32)
+    if wrong.any():
+        first = tuple(int(v) for v in np.argwhere(wrong)[0])
+        pytest.fail(f"variant {variant}, iters {iters}: {int(wrong.sum())} of {wrong.size} "
+                    f"accumulator registers wrong; chains hit {sorted(set(np.argwhere(wrong)[:, 2]))}; "
+                    f"first [block, thread, chain, register] = {first}: got {got[first]!r}, "
+                    f"want {ref[first]!r}")
+
+
+@pytest.mark.parametrize("variant,iters", [(0, 1), (0, 3), (0, 16), (1, 1), (1, 3), (1, 4),
+                                           (2, 1), (2, 3), (2, 4)])
+def test_mfma_peak_values_are_exact_on_integer_operands(variant, iters):
+    _assert_peak_exact(variant, iters)
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2])
+def test_mfma_peak_values_on_the_shipped_operands(variant):
+    """seed = 1e-3f as the timed driver passes it. |got − ref| ≤ γ·iters·Σ|a·b| with
+    γ = n·u/(1 − n·u), n = K·iters + 1 additions per element, u = 2^-23: the bound for any
+    order of additions, each rounded or truncated to fp32. One iteration missed or doubled is
+    off by 1/50 of Σ|a·b| where the terms share a sign (they all do: the operands are positive)."""
+    iters, seed = 50, np.float32(1e-3)
+    terms = _peak_terms(variant, seed)
+    kdim = terms.shape[-1]
+    n, u = kdim * iters + 1, 2.0 ** -23
+    gamma = n * u / (1 - n * u)
+    ref = iters * terms.sum(axis=-1)
+    bound = gamma * iters * np.abs(terms).sum(axis=-1)
+    assert gamma < 4e-4 and (np.abs(ref) > 50 * bound).all()    # a lost iteration is far outside
+    got = _peak_run(variant, iters, float(seed)).astype(np.float64)
+    err = np.abs(got - ref)
+    worst = np.unravel_index(np.argmax(err - bound), err.shape)
+    print(f"variant {variant}: max |err|/bound = {(err / bound).max():.3g}")
+    assert (err <= bound).all(), (f"[block, thread, chain, register] = {worst}: got {got[worst]}, "
+                                  f"want {ref[worst]}, bound {bound[worst]}")
+
+
+def test_mfma_peak_values_still_match_after_a_timed_run():
+    """The rate and the values meet: the timed driver leaves nothing behind that a values
+    launch of the kernel it times (variant 2) could see."""
+    assert probe.mfma_tflops(0, 2000) > 0
+    _assert_peak_exact(2, 3)
+
+
+# ------------------------------------------------------------------ 64² tile GEMM on exact data
+GEMM64_SHAPES = [(64, 64, 32),       # one block, one K-tile
+                 (64, 192, 64),      # bn runs, bm does not
+                 (192, 64, 96),      # the reverse, with an odd number of K-tiles
+                 (128, 192, 160)]    # both run, the grid is not square
+GEMM64_GUARD = 64
+
+
+def _gemm64_guarded(a, b, ref):
+    """Runs gemm_bf16 into a C between NaN guard rows; asserts C fully written, equal to ref bit
+    for bit, and the guards untouched."""
+    m, n = ref.shape
+    big = torch.full((m + 2 * GEMM64_GUARD, n), float("nan"), dtype=torch.float32, device=DEV)
+    nan_bits = big[:GEMM64_GUARD].view(torch.int32).clone()
+    out = big[GEMM64_GUARD:GEMM64_GUARD + m]
+    got = probe.gemm_bf16(a, b, out=out)
+    torch.cuda.synchronize()
+    assert got.data_ptr() == out.data_ptr()
+    unwritten = torch.isnan(out)
+    if unwritten.any():
+        tiles = sorted({(r // 64, c // 64) for r, c in unwritten.nonzero()[:4096].tolist()})
+        pytest.fail(f"{int(unwritten.sum())} elements of C never written, in tiles {tiles}")
+    wrong = out.view(torch.int32) != ref.view(torch.int32)
+    assert not wrong.any(), (f"{int(wrong.sum())} wrong elements, first at "
+                             f"{wrong.nonzero()[0].tolist()}")
+    assert torch.equal(big[:GEMM64_GUARD].view(torch.int32), nan_bits)
+    assert torch.equal(big[GEMM64_GUARD + m:].view(torch.int32), nan_bits)
+
+
+@pytest.mark.parametrize("m,n,k", GEMM64_SHAPES)
+def test_gemm_bf16_is_exact_on_small_integers_and_stays_inside_c(m, n, k):
+    """Integer operands in [-3, 3]: every partial sum is an integer of magnitude ≤ 9·K < 2^24,
+    exact in fp32 in any order, so C is the double product cast to fp32."""
+    g = torch.Generator(device=DEV).manual_seed(m * 31 + n * 7 + k)
+    a = torch.randint(-3, 4, (m, k), device=DEV, generator=g).to(torch.bfloat16)
+    b = torch.randint(-3, 4, (k, n), device=DEV, generator=g).to(torch.bfloat16)
+    assert 9 * k < 1 << 24
+    ref = (a.double() @ b.double()).to(torch.float32)
+    assert ref.abs().max() > 0
+    _gemm64_guarded(a, b, ref)
+
+
+def test_gemm_bf16_routes_every_row_of_b_through_a_permutation():
+    """A = a 64-row permutation matrix spread over K = 96 columns (32 of them empty), B with
+    12288 distinct bf16 entries: C[i] must be row perm[i] of B, bit for bit. Any slip in the
+    fragment maps, the two 8-wide k halves of a lane group included, pairs a row of A with the
+    wrong row of B, and no two rows or entries of B look alike."""
+    m, n, k = 64, 128, 96
+    perm = torch.randperm(k, generator=torch.Generator().manual_seed(96))[:m]
+    assert len(set(perm.tolist())) == m and set((perm // 8 % 2).tolist()) == {0, 1}
+    a = torch.zeros(m, k, dtype=torch.bfloat16)
+    a[torch.arange(m), perm] = 1.0
+    # bit patterns 0x3000 .. 0x5FFF: distinct, positive, finite and normal bf16 values
+    bits = (0x3000 + torch.arange(k * n, dtype=torch.int32)).to(torch.int16).view(k, n)
+    b = bits.view(torch.bfloat16)
+    assert bits.max() < 0x7F80 and torch.unique(b.float()).numel() == k * n
+    ref = b.float()[perm]
+    _gemm64_guarded(a.to(DEV), b.to(DEV).contiguous(), ref.to(DEV))
+
+
+def test_gemm_bf16_refuses_a_wrong_out_on_the_device():
+    a = torch.zeros(64, 32, dtype=torch.bfloat16, device=DEV)
+    b = torch.zeros(32, 64, dtype=torch.bfloat16, device=DEV)
+    for out in (torch.zeros(64, 64, dtype=torch.bfloat16, device=DEV),
+                torch.zeros(64, 32, dtype=torch.float32, device=DEV),
+                torch.zeros(64, 128, dtype=torch.float32, device=DEV)[:, ::2],
+                torch.zeros(64, 64, dtype=torch.float32)):
+        with pytest.raises(probe.ProbeError, match="out must be"):
+            probe.gemm_bf16(a, b, out=out)
+
+
 # ------------------------------------------------------------------ difference counter
 GRID = 2048 * 256                       # threads of k_count_diff = words per grid-stride sweep
 DIFF_SIZES = (16, 4096 - 16, (32 << 20) + 4112)
