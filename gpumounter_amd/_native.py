@@ -267,6 +267,15 @@ class CuscanResult(C.Structure):
                 ("seconds", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class CachescanPoke(C.Structure):     # gm_cachescan_poke_t
+    _fields_ = [("test", C.c_uint32), ("word_offset", C.c_uint32), ("mask", C.c_uint32)]
+
+
+class CachescanTiming(C.Structure):   # gm_cachescan_timing_t: [test][min, median, max]
+    _fields_ = [("first", (C.c_uint64 * 3) * 4), ("last", (C.c_uint64 * 3) * 4),
+                ("blocks", C.c_uint32), ("pad", C.c_uint32)]
+
+
 HOSTLINK_LEGS = 6             # native/include/gm_probe.h GM_HOSTLINK_LEGS
 HOSTLINK_MAX_RECORDS = 16     # GM_HOSTLINK_MAX_RECORDS
 HOSTLINK_MAX_BLOCKS = 1024    # GM_HOSTLINK_MAX_BLOCKS
@@ -436,6 +445,19 @@ def probe() -> C.CDLL:
         lib.gm_probe_lanescan_signature.argtypes = lib.gm_probe_cuscan_signature.argtypes
         lib.gm_probe_lanescan.argtypes = lib.gm_probe_cuscan.argtypes
         lib.gm_probe_lanescan_kernel_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.gm_probe_cachescan_expected.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32,
+                                                    C.POINTER(CachescanPoke),
+                                                    C.POINTER(C.c_uint32)]
+        lib.gm_probe_cachescan_signature.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32,
+                                                     C.POINTER(CachescanPoke), C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
+        lib.gm_probe_cachescan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int,
+                                           C.c_int, C.POINTER(CuscanInject),
+                                           C.POINTER(CachescanPoke), C.POINTER(CuscanResult),
+                                           C.POINTER(CuscanCu), C.c_int, C.POINTER(C.c_int),
+                                           C.POINTER(CachescanTiming)]
+        lib.gm_probe_cachescan_kernel_info.argtypes = [C.POINTER(C.c_int)] * 3
+        lib.gm_probe_cachescan_geometry.argtypes = [C.POINTER(C.c_uint32)] * 4
         lib.gm_probe_hostlink_geometry.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.gm_probe_hostlink_unroll.argtypes = [C.c_int]
         lib.gm_probe_hostlink_kwrite.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,

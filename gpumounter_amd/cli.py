@@ -28,6 +28,11 @@
                                        [--lane-scan-iters N] [--lane-scan-rounds N]
                                        [--lane-scan-inject ID|any:TEST:THREAD:WORD:MASK]
                                                   # per-CU register, lane and scalar-unit scan
+                                       [--cache-scan] [--cache-scan-tests l2,l1,scalar,icache]
+                                       [--cache-scan-iters N] [--cache-scan-rounds N]
+                                       [--cache-scan-inject ID|any:TEST:THREAD:WORD:MASK]
+                                       [--cache-scan-poke TEST:WORD_OFFSET:MASK]
+                                           # per-CU vector L1, L2, scalar and instruction caches
     python -m gpumounter_amd add    --master URL --ns NS --pod P -n 2 [--entire] [--lease 3600]
     python -m gpumounter_amd remove --master URL --ns NS --pod P --uuid U [--uuid U2] [--force]
     python -m gpumounter_amd status --master URL --node NODE
@@ -36,6 +41,7 @@
                                      [--gpu --memtest [SIZE]] [--gpu --cu-scan]
                                      [--gpu --host-link [SIZE]] [--gpu --atomics]
                                      [--gpu --mfma-scan] [--gpu --lane-scan]
+                                     [--gpu --cache-scan]
     python -m gpumounter_amd config-doc > docs/CONFIG.md   # every GM_* setting, from the source
 
 The reference ships only the two daemons and documents curl calls (QuickStart.md:41-92); the
@@ -274,6 +280,32 @@ def _add_lanescan(p, what: str) -> None:
                         "the scan must name it")
 
 
+def _cachescan_arg(kind):
+    """argparse type for the --cache-scan-* options: the parser in ops.cachescan, its refusal a
+    usage error."""
+    def conv(text):
+        from gpumounter_amd.ops import cachescan
+        try:
+            return getattr(cachescan, kind)(text)
+        except cachescan.ProbeError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    conv.__name__ = kind
+    return conv
+
+
+def _add_cachescan(p, what: str) -> None:
+    p.add_argument("--cache-scan", action="store_true", help=what)
+    p.add_argument("--cache-scan-inject", type=_cachescan_arg("parse_inject"), default=None,
+                   metavar="ID|any:TEST:THREAD:WORD:MASK",
+                   help="negative control: flip that signature word of that test on that CU; "
+                        "the scan must name it")
+    p.add_argument("--cache-scan-poke", type=_cachescan_arg("parse_poke"), default=None,
+                   metavar="TEST:WORD_OFFSET:MASK",
+                   help="negative control: flip that word of the test's data (l2, l1: of every "
+                        "block's segment after the fill; scalar: of the table); the test must "
+                        "find it")
+
+
 HOSTLINK_AUTO = -1    # --host-link without a SIZE: the test's default size
 
 
@@ -417,6 +449,32 @@ def cmd_probe(args) -> int:
             print(f"probe: --lane-scan-inject into {inj[1]!r}, which --lane-scan-tests leaves "
                   f"out", file=sys.stderr)
             return 2
+    if not args.cache_scan:
+        given = [o for o, v in (("--cache-scan-inject", args.cache_scan_inject),
+                                ("--cache-scan-poke", args.cache_scan_poke),
+                                ("--cache-scan-tests", args.cache_scan_tests),
+                                ("--cache-scan-iters", args.cache_scan_iters),
+                                ("--cache-scan-rounds", args.cache_scan_rounds)) if v is not None]
+        if given:
+            print(f"probe: {given[0]} needs --cache-scan", file=sys.stderr)
+            return 2
+    else:
+        from gpumounter_amd.ops import cachescan as _cs
+
+        if args.cache_scan_iters is not None and not 1 <= args.cache_scan_iters <= _cs.MAX_ITERS:
+            print(f"probe: --cache-scan-iters must be between 1 and {_cs.MAX_ITERS}",
+                  file=sys.stderr)
+            return 2
+        if args.cache_scan_rounds is not None and not 1 <= args.cache_scan_rounds <= 1024:
+            print("probe: --cache-scan-rounds must be between 1 and 1024", file=sys.stderr)
+            return 2
+        for opt, named in (("--cache-scan-inject", args.cache_scan_inject and
+                            args.cache_scan_inject[1]),
+                           ("--cache-scan-poke", args.cache_scan_poke and args.cache_scan_poke[0])):
+            if named and args.cache_scan_tests is not None and named not in args.cache_scan_tests:
+                print(f"probe: {opt} into {named!r}, which --cache-scan-tests leaves out",
+                      file=sys.stderr)
+                return 2
     if args.bdf:
         bdfs = args.bdf
     else:
@@ -485,6 +543,17 @@ def cmd_probe(args) -> int:
                 iters=args.lane_scan_iters or lanescan.DEFAULT_ITERS, min_rounds=rounds,
                 max_rounds=max(16, rounds), _inject=args.lane_scan_inject)
             bad |= not r["lanescan"]["ok"]
+    if args.cache_scan:
+        from gpumounter_amd.ops import cachescan
+
+        rounds = args.cache_scan_rounds or 1
+        for r in res:
+            r["cachescan"] = cachescan.scan(
+                r["device"], tests=args.cache_scan_tests or cachescan.ALL_TESTS,
+                iters=args.cache_scan_iters or cachescan.DEFAULT_ITERS, min_rounds=rounds,
+                max_rounds=max(16, rounds), _inject=args.cache_scan_inject,
+                _poke=args.cache_scan_poke)
+            bad |= not r["cachescan"]["ok"]
     print(json.dumps(res, indent=2))
     return 1 if bad else 0
 
@@ -663,10 +732,21 @@ def cmd_doctor(args) -> int:
         extra["lane_scan"] = True
         if args.lane_scan_inject:
             extra["lane_scan_inject"] = args.lane_scan_inject
+    for opt, v in (("--cache-scan-inject", args.cache_scan_inject),
+                   ("--cache-scan-poke", args.cache_scan_poke)):
+        if v and not args.cache_scan:
+            print(f"doctor: {opt} needs --cache-scan", file=sys.stderr)
+            return 2
+    if args.cache_scan:
+        extra["cache_scan"] = True
+        if args.cache_scan_inject:
+            extra["cache_scan_inject"] = args.cache_scan_inject
+        if args.cache_scan_poke:
+            extra["cache_scan_poke"] = args.cache_scan_poke
     checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
                         gpu=(args.gpu or bool(args.burn_in) or bool(memtest_bytes) or args.cu_scan
                              or args.host_link is not None or args.atomics or args.mfma_scan
-                             or args.lane_scan),
+                             or args.lane_scan or args.cache_scan),
                         burn_in_s=args.burn_in, memtest_bytes=memtest_bytes,
                         cu_scan=args.cu_scan, **extra)
     print(doctor.render(checks, args.json))
@@ -773,6 +853,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="units of work per test, 1..63 (default 16)")
     p.add_argument("--lane-scan-rounds", type=int, default=None, metavar="N",
                    help="at least N rounds (a round is one block per CU)")
+    _add_cachescan(p, "per-CU cache scan of every probed GPU: a march served by the L2, hit and "
+                      "replacement passes through the vector L1, a pointer chase through the "
+                      "scalar data cache and a body larger than the instruction cache on every "
+                      "compute unit (exit 1 on any wrong word)")
+    p.add_argument("--cache-scan-tests", type=_cachescan_arg("parse_tests"), default=None,
+                   metavar="a,b,...", help="of l2,l1,scalar,icache (default: all)")
+    p.add_argument("--cache-scan-iters", type=int, default=None, metavar="N",
+                   help="units of work per test, 1..63 (default 4)")
+    p.add_argument("--cache-scan-rounds", type=int, default=None, metavar="N",
+                   help="at least N rounds (a round is one block per CU)")
     p.set_defaults(fn=cmd_probe)
     for name, fn in (("add", cmd_add), ("remove", cmd_remove), ("status", cmd_status)):
         p = sub.add_parser(name)
@@ -819,6 +909,8 @@ def build_parser() -> argparse.ArgumentParser:
                      "is named with the format")
     _add_lanescan(p, "with --gpu: per-CU register, lane and scalar-unit scan of every GPU; a "
                      "failing CU is named with the test")
+    _add_cachescan(p, "with --gpu: per-CU cache scan (vector L1, L2, scalar and instruction "
+                      "caches) of every GPU; a failing CU is named with the test")
     p.set_defaults(fn=cmd_doctor)
     p = sub.add_parser("bpf-dump")
     p.add_argument("--allow", action="append", default=[])

@@ -9,9 +9,9 @@ id the block read from the hardware registers. The signature is a pure function 
 iters, thread) (formulas: native/include/gm_probe.h); :func:`expected` evaluates it without a GPU
 and :func:`signature` returns what one block computed.
 
-What it cannot tell: clocks and thermals and the vector and instruction caches are not covered
-(transcendental units, register-file addressing, the scalar unit and the cross-lane network are
-in :mod:`gpumounter_amd.ops.lanescan`); a CU id is a label from the hardware registers, not a verified die position; and where
+What it cannot tell: clocks and thermals are not covered (transcendental units, register-file
+addressing, the scalar unit and the cross-lane network are in :mod:`gpumounter_amd.ops.lanescan`,
+the vector L1, L2, scalar and instruction caches in :mod:`gpumounter_amd.ops.cachescan`); a CU id is a label from the hardware registers, not a verified die position; and where
 blocks run is up to the dispatcher, so on a GPU that is in use some CUs may not be reached
 (``complete`` is false then, which is not an error: ``ok`` says whether a wrong word was seen).
 No silent fallback: a missing ``libgm_probe.so`` or a HIP failure raises.

@@ -23,9 +23,9 @@ what the ISA document says the instruction does. :func:`expected` evaluates it w
 :func:`signature` returns what one block computed.
 
 What it cannot tell: the scaled conversion instructions, rounding, NaN, infinity and subnormal
-behaviour, transcendental results at points that are not exact, the sign of a zero result, the
-vector L1 and L2 caches, the instruction cache, LDS atomics, clocks and thermals are not covered;
-and as for the CU scan, a CU id is a label and ``complete`` says whether every CU was reached. No
+behaviour, transcendental results at points that are not exact, the sign of a zero result, LDS
+atomics, clocks and thermals are not covered (the vector L1, L2, scalar and instruction caches
+are in :mod:`gpumounter_amd.ops.cachescan`); and as for the CU scan, a CU id is a label and ``complete`` says whether every CU was reached. No
 silent fallback: a missing ``libgm_probe.so`` or a HIP failure raises.
 """
 from __future__ import annotations

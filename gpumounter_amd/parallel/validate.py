@@ -29,7 +29,11 @@ starting a job on them — the reference offers nothing here:
 10. optionally (``--lane-scan``) the per-CU register, lane and scalar-unit scan on all GPUs at once
    (:func:`gpumounter_amd.ops.lanescan.scan`): bit-exact cross-lane moves, a register-file march,
    a scalar chain, transcendentals at exact points, fp64 and packed arithmetic on every compute
-   unit.
+   unit;
+11. optionally (``--cache-scan``) the per-CU cache scan on all GPUs at once
+   (:func:`gpumounter_amd.ops.cachescan.scan`): a march served by the L2, hit and replacement
+   passes through the vector L1, a pointer chase through the scalar data cache and a body larger
+   than the instruction cache on every compute unit.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -111,7 +115,27 @@ def main(argv=None) -> int:
                     help="then the per-CU register, lane and scalar-unit scan on every GPU at once")
     ap.add_argument("--lane-scan-inject", default=None, metavar="ID|any:TEST:THREAD:WORD:MASK",
                     help="its negative control (see probe --lane-scan-inject); needs --lane-scan")
+    ap.add_argument("--cache-scan", action="store_true",
+                    help="then the per-CU cache scan (vector L1, L2, scalar and instruction "
+                         "caches) on every GPU at once")
+    ap.add_argument("--cache-scan-inject", default=None, metavar="ID|any:TEST:THREAD:WORD:MASK",
+                    help="its negative control (see probe --cache-scan-inject); needs --cache-scan")
+    ap.add_argument("--cache-scan-poke", default=None, metavar="TEST:WORD_OFFSET:MASK",
+                    help="its data poke (see probe --cache-scan-poke); needs --cache-scan")
     args = ap.parse_args(argv)
+    cache_scan_inject = cache_scan_poke = None
+    if args.cache_scan_inject is not None or args.cache_scan_poke is not None:
+        from gpumounter_amd.ops import cachescan
+        if not args.cache_scan:
+            ap.error(("--cache-scan-inject" if args.cache_scan_inject is not None
+                      else "--cache-scan-poke") + " needs --cache-scan")
+        try:
+            if args.cache_scan_inject is not None:
+                cache_scan_inject = cachescan.parse_inject(args.cache_scan_inject)
+            if args.cache_scan_poke is not None:
+                cache_scan_poke = cachescan.parse_poke(args.cache_scan_poke)
+        except cachescan.ProbeError as e:
+            ap.error(str(e))
     lane_scan_inject = None
     if args.lane_scan_inject is not None:
         from gpumounter_amd.ops import lanescan
@@ -255,6 +279,18 @@ def main(argv=None) -> int:
             del m["per_cu"]               # as for the CU scan: "failed" names the bad ones
         report["lanescan"] = ls
         report["ok"] &= all(m["ok"] for m in ls)
+    if args.cache_scan and not args.cpu_ranks:
+        from concurrent.futures import ThreadPoolExecutor
+
+        from gpumounter_amd.ops import cachescan
+
+        with ThreadPoolExecutor(max_workers=world) as ex:
+            cs = list(ex.map(lambda d: cachescan.scan(d, _inject=cache_scan_inject,
+                                                      _poke=cache_scan_poke), range(world)))
+        for m in cs:
+            del m["per_cu"]               # as for the CU scan: "failed" names the bad ones
+        report["cachescan"] = cs
+        report["ok"] &= all(m["ok"] for m in cs)
     print(json.dumps(report))
     return 0 if report["ok"] else 1
 

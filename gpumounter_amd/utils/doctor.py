@@ -286,7 +286,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                host_link_flip=None, atomics: bool = False,
                atomics_inject=None, mfma_scan: bool = False,
                mfma_scan_inject=None, lane_scan: bool = False,
-               lane_scan_inject=None) -> List[Check]:
+               lane_scan_inject=None, cache_scan: bool = False,
+               cache_scan_inject=None, cache_scan_poke=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
@@ -309,8 +310,11 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     ``mfma_scan_inject`` is its negative control. With ``lane_scan`` also the per-CU register,
     lane and scalar-unit scan (:func:`gpumounter_amd.ops.lanescan.scan`): a CU with a wrong
     signature word fails the check and is named the same way, with the test; a scan that did not
-    reach every CU is stated, not failed; ``lane_scan_inject`` is its negative control. A GPU that
-    fails here should not be handed out."""
+    reach every CU is stated, not failed; ``lane_scan_inject`` is its negative control. With
+    ``cache_scan`` also the per-CU cache scan (:func:`gpumounter_amd.ops.cachescan.scan`: vector
+    L1, L2, scalar and instruction caches), failed, named and stated in the same way;
+    ``cache_scan_inject`` and ``cache_scan_poke`` are its negative controls. A GPU that fails here
+    should not be handed out."""
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import probe
 
@@ -420,6 +424,18 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                 if not m["ok"]:
                     detail += f", failed: {lanescan.describe_failed(m)}"
                     status = "fail"
+            if cache_scan:
+                from gpumounter_amd.ops import cachescan
+
+                m = cachescan.scan(d, _inject=cache_scan_inject, _poke=cache_scan_poke)
+                detail += (f", cache-scan {len(m['tests'])} tests {m['cus_seen']}/"
+                           f"{m['cus_expected']} CUs in {m['rounds']} round(s) "
+                           f"{m['kernel_ms']:.2f} ms {m['words_in_error']} wrong words")
+                if not m["complete"]:
+                    detail += " (incomplete: not every CU was reached)"
+                if not m["ok"]:
+                    detail += f", failed: {cachescan.describe_failed(m)}"
+                    status = "fail"
             out.append(Check(f"gpu{d}", status, detail))
         except Exception as e:  # noqa: BLE001 - a faulting GPU is exactly what this finds
             out.append(Check(f"gpu{d}", "fail", f"probe failed: {e}"))
@@ -433,7 +449,8 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         burn_in_s: float = 0.0, *, memtest_bytes: int = 0, cu_scan: bool = False,
         host_link_bytes: int = 0, atomics: bool = False, atomics_inject=None,
         mfma_scan: bool = False, mfma_scan_inject=None, lane_scan: bool = False,
-        lane_scan_inject=None) -> List[Check]:
+        lane_scan_inject=None, cache_scan: bool = False, cache_scan_inject=None,
+        cache_scan_poke=None) -> List[Check]:
     checks = check_inventory(cfg) + check_cgroup(cfg) + check_devnodes(cfg) + \
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
@@ -452,6 +469,12 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
             extra["lane_scan"] = True
             if lane_scan_inject is not None:
                 extra["lane_scan_inject"] = lane_scan_inject
+        if cache_scan:
+            extra["cache_scan"] = True
+            if cache_scan_inject is not None:
+                extra["cache_scan_inject"] = cache_scan_inject
+            if cache_scan_poke is not None:
+                extra["cache_scan_poke"] = cache_scan_poke
         checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes, **extra)
     if not skip_cluster:
         async def both():

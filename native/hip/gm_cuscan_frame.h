@@ -1,4 +1,5 @@
-// gm_cuscan_frame.h — the frame the per-CU scans share (gm_cuscan.hip, gm_mfmascan.hip): where a
+// gm_cuscan_frame.h — the frame the per-CU scans share (gm_cuscan.hip, gm_mfmascan.hip,
+// gm_lanescan.hip, gm_cachescan.hip): where a
 // block runs, the result table, the compare of one test's signature with the host's table, the
 // block-outcome reduction, the round loop and the decode into gm_cuscan_cu_t.
 //
@@ -169,10 +170,13 @@ inline bool rounds_ok(int min_rounds, int max_rounds, const gm_cuscan_cu_t* cus,
 // The scan of device `dev` with the compare form of a scan kernel; the arguments were checked.
 // `fill` writes the expected table (exp_words words, zeroed) on the host: a unit that computes
 // wrongly must not produce its own.
-template <class Fill>
-int run_scan(int dev, ScanKernel kernel, const Params& p, size_t exp_words, Fill fill,
-             int min_rounds, int max_rounds, gm_cuscan_result_t* out, gm_cuscan_cu_t* cus,
-             int cus_cap, int* n_cus) {
+// `launch(blocks, expected, tab)` enqueues one round of `blocks` blocks of the compare form of
+// `kernel` on the null stream and returns a HIP error code: a scan whose kernel takes more than
+// ScanKernel's arguments brings its own.
+template <class Fill, class Launch>
+int run_scan_with(int dev, const void* kernel, size_t exp_words, Fill fill, Launch launch,
+                  int min_rounds, int max_rounds, gm_cuscan_result_t* out, gm_cuscan_cu_t* cus,
+                  int cus_cap, int* n_cus) {
   DeviceGuard g(dev);
   if (!g.ok) return (int)hipErrorInvalidDevice;
   const double t0 = now_s();
@@ -192,7 +196,7 @@ int run_scan(int dev, ScanKernel kernel, const Params& p, size_t exp_words, Fill
   {
     // loads the code object here, not between a timed pair of events
     hipFuncAttributes attr;
-    GM_CHECK(hipFuncGetAttributes(&attr, (const void*)kernel));
+    GM_CHECK(hipFuncGetAttributes(&attr, kernel));
   }
   DevTable* tab = (DevTable*)dtab.p;
 
@@ -201,9 +205,7 @@ int run_scan(int dev, ScanKernel kernel, const Params& p, size_t exp_words, Fill
   double ms_sum = 0;
   while (rounds < max_rounds) {
     GM_CHECK(hipEventRecord(ev.e0, nullptr));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)cu_count), dim3(GM_CUSCAN_THREADS), 0, nullptr, p,
-                       (const uint32_t*)dexp.p, tab, (uint32_t*)nullptr, (uint32_t*)nullptr);
-    GM_CHECK(hipGetLastError());
+    if (int e = launch(cu_count, (const uint32_t*)dexp.p, tab)) return e;
     GM_CHECK(hipEventRecord(ev.e1, nullptr));
     GM_CHECK(hipMemcpy(&distinct, &tab->distinct, sizeof(distinct), hipMemcpyDeviceToHost));
     float ms = 0;
@@ -250,6 +252,21 @@ int run_scan(int dev, ScanKernel kernel, const Params& p, size_t exp_words, Fill
   out->kernel_ms = ms_sum;
   out->seconds = now_s() - t0;
   return 0;
+}
+
+// The scan with a kernel of ScanKernel's signature.
+template <class Fill>
+int run_scan(int dev, ScanKernel kernel, const Params& p, size_t exp_words, Fill fill,
+             int min_rounds, int max_rounds, gm_cuscan_result_t* out, gm_cuscan_cu_t* cus,
+             int cus_cap, int* n_cus) {
+  return run_scan_with(
+      dev, (const void*)kernel, exp_words, fill,
+      [&](int blocks, const uint32_t* expected, DevTable* tab) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(GM_CUSCAN_THREADS), 0, nullptr, p,
+                           expected, tab, (uint32_t*)nullptr, (uint32_t*)nullptr);
+        return (int)hipGetLastError();
+      },
+      min_rounds, max_rounds, out, cus, cus_cap, n_cus);
 }
 
 }  // namespace

@@ -279,9 +279,9 @@ int gm_probe_memtest_store_variant(int nontemporal);
 //                          in phase 3 was first written by the next wave; of the permuted reads
 //                          of phase 2 about three in four are of a word another wave wrote.
 //
-// What the scan cannot see: clocks, thermals, the vector and instruction caches (the
-// transcendental units, register-file addressing, the scalar unit and the cross-lane network are
-// the lane scan's, below).
+// What the scan cannot see: clocks and thermals (the transcendental units, register-file
+// addressing, the scalar unit and the cross-lane network are the lane scan's, the vector L1, L2,
+// scalar and instruction caches the cache scan's, both below).
 // The GM_CUSCAN_* test bits and the iters limits are defined in gm_cuscan_sig.h.
 #define GM_CUSCAN_MAX_RECORDS 16
 #define GM_CUSCAN_IDS 4096
@@ -522,8 +522,8 @@ int gm_probe_mfmascan(int dev, uint32_t formats_mask, uint32_t iters, uint64_t s
 // static_asserts in gm_lanescan_ref.h hold every cap). A zero product of a negative factor is -0.
 //
 // Not covered: v_sqrt_f64 (above), v_cvt_scalef32_*, rounding, NaN, infinity and subnormal
-// behaviour, transcendental results at points that are not exact, the vector L1 and L2 caches,
-// the instruction cache, LDS atomics, clocks and thermals.
+// behaviour, transcendental results at points that are not exact, LDS atomics, clocks and
+// thermals. The vector L1, L2, scalar and instruction caches are the cache scan's, below.
 //
 // The records, the injection, the per-CU entries and the result are the CU scan's, with `test`
 // and `tests_failed` holding GM_LANESCAN_* bits. Arguments and the up-front hipErrorInvalidValue
@@ -544,6 +544,127 @@ int gm_probe_lanescan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t see
 // numRegs and localSizeBytes of the scan kernel from hipFuncGetAttributes on the current device.
 // The register march is a register march only while *scratch_bytes is 0.
 int gm_probe_lanescan_kernel_info(int* num_regs, int* scratch_bytes);
+
+// ------------------------------------------------------------------ cache scan
+// The CU scan's frame a fourth time, around the SRAM between the registers and HBM: the CU's
+// vector L1, its XCC's L2, the scalar data cache and the instruction cache. Four tests of 4
+// signature words per thread t (wave w = t / 64, lane l = t % 64); the code is
+// gm_cachescan_ref.h. H is the CU scan's hash; fold(s, v) = rotl32(s, 5) + v.
+//
+//   bit  name    per unit of iters
+//     1  l2      1 round of the march
+//     2  l1      1 hit pass (the fill and the replacement sweep run once)
+//     4  scalar  64 steps of the chain
+//     8  icache  1 execution of the body
+//
+// The arena. The driver allocates blocks x GM_CACHESCAN_SEG_BYTES (64 KiB, 16384 words) of device
+// memory; block b touches segment b and no other byte, so nothing depends on placement and no
+// block waits for another. Word a of segment b holds P(r, a) ^ K(b), P(r, a) = H(0x400, 65536 r +
+// a), K(b) = H(0x401, b). The kernel removes K(b) from what it loads before it folds: the
+// signature does not depend on b, and a line served from another block's segment decodes wrongly.
+// The device writes the data; the host computes the folds from scratch in an array of its own.
+// A fill: thread t writes the 16-byte elements v = 256 k + t, k < 16, with plain 128-bit stores
+// (plain stores keep the line in the XCC's L2); barrier.
+//
+// l2. Every load bypasses the vector L1 and is served by the L2: the 32-bit ones are agent-scope
+// relaxed atomic loads (global_load_dword sc1), the 128-bit ones nontemporal loads
+// (global_load_dwordx4 nt). s0 = s1 = s2 = s3 = 0; per round r < iters:
+//   1. fill with P(r, .)
+//   2. for i < 64: a = ((256 i + t) * 6151 + 3) % 16384 (a permutation: the stride is odd);
+//      32-bit read g; s0 = rotl32(s0, 5) + g; s3 += (g != P(r, a)); plain write of ~g; barrier
+//   3. for k < 16: 128-bit read of element v = 256 k + (t + 64) % 256, first written by the next
+//      wave, and for each of its words g, c = 0..3: s1 = rotl32(s1, 7) ^ g; s2 += g;
+//      s3 += (g != ~P(r, 4v + c)); barrier
+// Words s0..s3; s3, the mismatches seen in flight, is 0 on a healthy unit.
+//
+// l1. One fill with P(64, .). A probe of word a is a plain load g1 (through the L1), then the
+// 32-bit bypass load g2 of the same word: s0 = fold(s0, g1); s1 = fold(s1, g2); s2 += (g1 != g2);
+// s3 += (g1 != P(64, a)). The address is made opaque to the compiler before each probe, so every
+// probe is two loads.
+//   (a) hit phase, iters passes over the first 16 KiB: for i < 16, j = ((64 i + l) * 389 + 11) %
+//       1024, probe a = 1024 (j / 256) + 256 ((w + 1) % 4) + j % 256. Wave w filled the words with
+//       (a / 256) % 4 == w, so every line is read by the wave after the one that filled it, and
+//       a wave's 1024 (i, l) pairs are a permutation of its 1024 words. A pass issues its 16
+//       plain loads first, then the 16 bypass loads; the folds are per probe, in the order of i.
+//   (b) replacement phase, once over all 64 KiB (twice the 32 KiB the L1 is taken to hold): for
+//       i < 64, a = ((256 i + t) * 4099 + 5) % 16384, probe a twice in succession.
+// Words s0..s3. In the host table s0 == s1 and s2 == 0 (s3 == 0 without a poke). s0 wrong with s1
+// right names the CU's L1; both wrong names the L2 or memory.
+//
+// scalar. T[i] = H(0x410, i), i < 8192 (32 KiB, in a buffer of its own), read through a const
+// __restrict__ kernel argument at a wave-uniform index: scalar loads. Per wave i = H(0x411, 4 w) %
+// 8192, a = H(0x411, 4 w + 1), b = H(0x411, 4 w + 2); v_n = H(0x412, 4 t + n). Step s < 64 iters:
+//   k = T[i];  a = rotl32(a, 5) + k;  b = (b ^ a) * 0x9E3779B1;  b ^= b >> 15
+//   m = ((i ^ k) + s) * 0x85EBCA6B;  m ^= m >> 13;  i = m % 8192     (the next index depends on k)
+//   v_{s & 3} = rotl32(v_{s & 3}, 7) + (a ^ l * 0x01000193);  v_{(s + 2) & 3} ^= b + l
+// Words v_0..v_3.
+//
+// icache. x = H(0x420, 2 t), y = H(0x420, 2 t + 1), sx = sy = 0. The body is
+// GM_CACHESCAN_ICACHE_STEPS distinct steps in a straight line, expanded at compile time, each with
+// three 32-bit literals of its own, C(j, n) = the finalizer below of 4 j + n:
+//   h = (4 j + n) * 0x9E3779B1 + 0x7F4A7C15;  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;
+//   h *= 0xC2B2AE35;  h ^= h >> 16
+//   step j:  x = rotl32(x, 1 + j % 31) + C(j, 0);  x ^= y;  x *= C(j, 1) | 1
+//            y = rotl32(y, 1 + (j / 31) % 31) ^ x;  y += C(j, 2)
+// It is executed iters times, and after each execution sx = fold(sx, x), sy = fold(sy, y). Words
+// x, y, sx, sy. The body is a function of its own that reads the program counter at its two ends:
+// the difference is its span in bytes, which must be at least 128 KiB (twice the 64 KiB
+// instruction cache a pair of CUs is taken to share) for the test to mean what it says.
+//
+// Residency is observed, never judged: thread 0 stores the shader-clock (s_memtime) counts of each
+// test's first and last pass (l2: round; l1: the plain loads of a hit pass; scalar: 64 steps;
+// icache: execution) to a
+// side buffer [block][test][2], and the driver reports min / median / max over the blocks of the
+// last round. `ok` never depends on them.
+//
+// Not covered: the Infinity Cache (nothing addresses it), LDS atomics, clocks and thermals; the
+// L1 and instruction-cache sizes are assumptions, and a corrupted instruction may fault instead
+// of computing a wrong word.
+//
+// The records, the injection, the per-CU entries and the result are the CU scan's, with `test`
+// and `tests_failed` holding GM_CACHESCAN_* bits; 1 <= iters <= GM_CACHESCAN_MAX_ITERS. Every
+// argument check comes before any HIP call.
+//
+// Second negative control, through the real detection path: after the named test's fill and
+// barrier (l2: the first round's), thread 0 of every block XORs `mask` into word `word_offset` of
+// its own segment with a plain store. For `scalar` the host flips that word of the uploaded
+// table. The scan still compares with the table of a clean run, so the poked word is found by the
+// test itself; gm_probe_cachescan_expected with the poke gives the exact signature of the poked
+// run (a table word the chain never reads changes nothing). `icache` has no data to poke.
+// hipErrorInvalidValue for a test that has no data or is not
+// selected, an offset beyond the segment (16384 words) or table (8192 words), or mask == 0.
+typedef struct gm_cachescan_poke {
+  uint32_t test, word_offset, mask;
+} gm_cachescan_poke_t;
+
+// Shader-clock counts of the first and the last pass of test index i (bit 1 << i), as
+// {min, median, max} over the blocks of the last round; 0 for a test that was not run.
+typedef struct gm_cachescan_timing {
+  uint64_t first[4][3];
+  uint64_t last[4][3];
+  uint32_t blocks;
+  uint32_t pad;
+} gm_cachescan_timing_t;
+
+// The expected table of `test`, in a run with `poke` (null: none). A poke of another test leaves
+// it alone. Host only, needs no GPU.
+int gm_probe_cachescan_expected(uint32_t test, uint64_t seed, uint32_t iters,
+                                const gm_cachescan_poke_t* poke, uint32_t* out);
+// One block, raw, on an arena of its own. It returns after the block has run.
+int gm_probe_cachescan_signature(uint32_t test, uint64_t seed, uint32_t iters,
+                                 const gm_cachescan_poke_t* poke, uint32_t* dev_out,
+                                 uint32_t* dev_where, void* stream);
+// The scan. `inject`, `poke` and `timing` may be null.
+int gm_probe_cachescan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed, int min_rounds,
+                       int max_rounds, const gm_cuscan_inject_t* inject,
+                       const gm_cachescan_poke_t* poke, gm_cuscan_result_t* out, gm_cuscan_cu_t* cus,
+                       int cus_cap, int* n_cus, gm_cachescan_timing_t* timing);
+// numRegs and localSizeBytes of the scan kernel on the current device, and the span of the
+// icache body in bytes, from the program counter at its two ends (one block runs the body once).
+int gm_probe_cachescan_kernel_info(int* num_regs, int* scratch_bytes, int* icache_body_bytes);
+// GM_CACHESCAN_SEG_BYTES, _L1_HIT_BYTES, _TABLE_BYTES, _ICACHE_STEPS. Host only.
+int gm_probe_cachescan_geometry(uint32_t* seg_bytes, uint32_t* l1_hit_bytes, uint32_t* table_bytes,
+                                uint32_t* icache_steps);
 
 // ------------------------------------------------------------------ host link (PCIe) test
 // Moves checked bytes between pinned host memory and the GPU, in both directions, by the copy
