@@ -204,19 +204,6 @@ def _burn_in_flip(text):
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
-def _cuscan_arg(kind):
-    """argparse type for the --cu-scan-* options: the parser in ops.cuscan, its refusal a usage
-    error."""
-    def conv(text):
-        from gpumounter_amd.ops import cuscan
-        try:
-            return getattr(cuscan, kind)(text)
-        except cuscan.ProbeError as e:
-            raise argparse.ArgumentTypeError(str(e)) from None
-    conv.__name__ = kind
-    return conv
-
-
 def _atomics_arg(kind):
     """argparse type for the --atomics-* options: the parser in ops.atomics, its refusal a usage
     error."""
@@ -238,72 +225,100 @@ def _add_atomics(p, what: str) -> None:
                         "handoff:BLOCK:ROUND:WORD:MASK; the test must report it")
 
 
-def _mfmascan_arg(kind):
-    """argparse type for the --mfma-scan-* options: the parser in ops.mfmascan, its refusal a
+def _scans():
+    from gpumounter_amd.ops import cuframe
+
+    return cuframe.registry()
+
+
+def _scan_arg(scan, kind):
+    """argparse type for a per-CU scan's options: the parser in the scan's module, its refusal a
     usage error."""
     def conv(text):
-        from gpumounter_amd.ops import mfmascan
+        from gpumounter_amd.ops.probe import ProbeError
         try:
-            return getattr(mfmascan, kind)(text)
-        except mfmascan.ProbeError as e:
+            return getattr(scan.module, kind)(text)
+        except ProbeError as e:
             raise argparse.ArgumentTypeError(str(e)) from None
     conv.__name__ = kind
     return conv
 
 
-def _add_mfmascan(p, what: str) -> None:
-    p.add_argument("--mfma-scan", action="store_true", help=what)
-    p.add_argument("--mfma-scan-inject", type=_mfmascan_arg("parse_inject"), default=None,
-                   metavar="ID|any:FORMAT:THREAD:WORD:MASK",
-                   help="negative control: flip that accumulator word of that format on that CU; "
-                        "the scan must name it")
+def _add_controls(p, scan) -> None:
+    for name, (metavar, text, _) in scan.controls.items():
+        p.add_argument(f"--{scan.label}-{name}", type=_scan_arg(scan, f"parse_{name}"),
+                       default=None, metavar=metavar, help=text)
 
 
-def _lanescan_arg(kind):
-    """argparse type for the --lane-scan-* options: the parser in ops.lanescan, its refusal a
-    usage error."""
-    def conv(text):
-        from gpumounter_amd.ops import lanescan
-        try:
-            return getattr(lanescan, kind)(text)
-        except lanescan.ProbeError as e:
-            raise argparse.ArgumentTypeError(str(e)) from None
-    conv.__name__ = kind
-    return conv
+def _add_probe_scan(p, scan) -> None:
+    """probe's options of one scan: the scan and its controls, its selection, iterations and
+    rounds."""
+    p.add_argument(f"--{scan.label}", action="store_true",
+                   help=f"{scan.title} of every probed GPU: {scan.does} on every compute unit "
+                        f"(exit 1 on any wrong word)")
+    if not scan.plain_cli:
+        _add_controls(p, scan)
+    p.add_argument(f"--{scan.label}-{scan.selection}",
+                   type=_scan_arg(scan, f"parse_{scan.selection}"), metavar="a,b,...",
+                   default=scan.all if scan.plain_cli else None,
+                   help=None if scan.plain_cli else f"of {','.join(scan.all)} (default: all)")
+    if scan.iters_unit:
+        p.add_argument(f"--{scan.label}-iters", type=int, default=None, metavar="N",
+                       help=f"{scan.iters_unit}, 1..{scan.max_iters} (default "
+                            f"{scan.default_iters})")
+    p.add_argument(f"--{scan.label}-rounds", type=int, default=1 if scan.plain_cli else None,
+                   metavar="N", help="at least N rounds (a round is one block per CU)")
+    if scan.plain_cli:
+        _add_controls(p, scan)      # the CU scan lists its own last
 
 
-def _add_lanescan(p, what: str) -> None:
-    p.add_argument("--lane-scan", action="store_true", help=what)
-    p.add_argument("--lane-scan-inject", type=_lanescan_arg("parse_inject"), default=None,
-                   metavar="ID|any:TEST:THREAD:WORD:MASK",
-                   help="negative control: flip that signature word of that test on that CU; "
-                        "the scan must name it")
+def _add_doctor_scan(p, scan) -> None:
+    p.add_argument(f"--{scan.label}", action="store_true",
+                   help=f"with --gpu: {scan.title}{scan.covers} of every GPU; a failing CU is named"
+                        + ("" if scan.plain_cli else f" with the {scan.unit}"))
+    if not scan.plain_cli:
+        _add_controls(p, scan)
 
 
-def _cachescan_arg(kind):
-    """argparse type for the --cache-scan-* options: the parser in ops.cachescan, its refusal a
-    usage error."""
-    def conv(text):
-        from gpumounter_amd.ops import cachescan
-        try:
-            return getattr(cachescan, kind)(text)
-        except cachescan.ProbeError as e:
-            raise argparse.ArgumentTypeError(str(e)) from None
-    conv.__name__ = kind
-    return conv
+def _scan_usage(scan, args, tool: str) -> Optional[str]:
+    """What is wrong with the scan's options on ``tool``'s command line (None: nothing), checked
+    before any GPU work."""
+    from gpumounter_amd.ops.cuframe import MAX_ROUNDS
+
+    got = {name: getattr(args, f"{scan.stem}_{name}", None)
+           for name in (*scan.controls, scan.selection, "iters", "rounds")}
+    if not getattr(args, scan.stem):
+        given = [n for n, v in got.items() if v is not None and not (
+            scan.plain_cli and n in (scan.selection, "rounds"))]      # those have defaults
+        if given:
+            return f"{tool}: --{scan.label}-{given[0]} needs --{scan.label}"
+    if got["iters"] is not None and not 1 <= got["iters"] <= scan.max_iters:
+        return f"{tool}: --{scan.label}-iters must be between 1 and {scan.max_iters}"
+    if got["rounds"] is not None and not 1 <= got["rounds"] <= MAX_ROUNDS:
+        return f"{tool}: --{scan.label}-rounds must be between 1 and {MAX_ROUNDS}"
+    for name in scan.controls:
+        # an injection names its test after the CU, a poke first
+        named = got[name] and got[name][1 if name == "inject" else 0]
+        if named and got[scan.selection] is not None and named not in got[scan.selection]:
+            return (f"{tool}: --{scan.label}-{name} into {named!r}, which "
+                    f"--{scan.label}-{scan.selection} leaves out")
+    return None
 
 
-def _add_cachescan(p, what: str) -> None:
-    p.add_argument("--cache-scan", action="store_true", help=what)
-    p.add_argument("--cache-scan-inject", type=_cachescan_arg("parse_inject"), default=None,
-                   metavar="ID|any:TEST:THREAD:WORD:MASK",
-                   help="negative control: flip that signature word of that test on that CU; "
-                        "the scan must name it")
-    p.add_argument("--cache-scan-poke", type=_cachescan_arg("parse_poke"), default=None,
-                   metavar="TEST:WORD_OFFSET:MASK",
-                   help="negative control: flip that word of the test's data (l2, l1: of every "
-                        "block's segment after the fill; scalar: of the table); the test must "
-                        "find it")
+def _run_scan(scan, args, res) -> bool:
+    """The scan, if it was asked for, on every probed GPU, booked under its key in ``res``;
+    false: one found an error."""
+    if not getattr(args, scan.stem):
+        return True
+    rounds = getattr(args, f"{scan.stem}_rounds") or 1
+    kw = {scan.selection: getattr(args, f"{scan.stem}_{scan.selection}") or scan.all}
+    if scan.iters_unit:
+        kw["iters"] = getattr(args, f"{scan.stem}_iters") or scan.default_iters
+    kw.update(min_rounds=rounds, max_rounds=max(16, rounds))
+    kw.update({f"_{name}": getattr(args, f"{scan.stem}_{name}") for name in scan.controls})
+    for r in res:
+        r[scan.key] = scan.run(r["device"], **kw)
+    return all(r[scan.key]["ok"] for r in res)
 
 
 HOSTLINK_AUTO = -1    # --host-link without a SIZE: the test's default size
@@ -342,15 +357,10 @@ def cmd_probe(args) -> int:
     if args.burn_in_flip and not args.burn_in:
         print("probe: --burn-in-flip needs --burn-in SECONDS", file=sys.stderr)
         return 2                      # a usage error, not a failed burn-in (exit 1)
-    if args.cu_scan_inject and not args.cu_scan:
-        print("probe: --cu-scan-inject needs --cu-scan", file=sys.stderr)
-        return 2
-    if not 1 <= args.cu_scan_rounds <= 1024:
-        print("probe: --cu-scan-rounds must be between 1 and 1024", file=sys.stderr)
-        return 2
-    if args.cu_scan_inject and args.cu_scan_inject[1] not in args.cu_scan_tests:
-        print(f"probe: --cu-scan-inject into {args.cu_scan_inject[1]!r}, which --cu-scan-tests "
-              f"leaves out", file=sys.stderr)
+    cu, *later = _scans()             # the CU scan: before the host-link and atomics tests
+    error = _scan_usage(cu, args, "probe")
+    if error:
+        print(error, file=sys.stderr)
         return 2
     if args.host_link is None:
         given = [o for o, v in (("--host-link-flip", args.host_link_flip),
@@ -403,78 +413,11 @@ def cmd_probe(args) -> int:
             print(f"probe: --atomics-inject into {inj[0]!r}, which --atomics-tests leaves out",
                   file=sys.stderr)
             return 2
-    if not args.mfma_scan:
-        given = [o for o, v in (("--mfma-scan-inject", args.mfma_scan_inject),
-                                ("--mfma-scan-formats", args.mfma_scan_formats),
-                                ("--mfma-scan-iters", args.mfma_scan_iters),
-                                ("--mfma-scan-rounds", args.mfma_scan_rounds)) if v is not None]
-        if given:
-            print(f"probe: {given[0]} needs --mfma-scan", file=sys.stderr)
+    for scan in later:
+        error = _scan_usage(scan, args, "probe")
+        if error:
+            print(error, file=sys.stderr)
             return 2
-    else:
-        from gpumounter_amd.ops import mfmascan as _ms
-
-        if args.mfma_scan_iters is not None and not 1 <= args.mfma_scan_iters <= _ms.MAX_ITERS:
-            print(f"probe: --mfma-scan-iters must be between 1 and {_ms.MAX_ITERS}",
-                  file=sys.stderr)
-            return 2
-        if args.mfma_scan_rounds is not None and not 1 <= args.mfma_scan_rounds <= 1024:
-            print("probe: --mfma-scan-rounds must be between 1 and 1024", file=sys.stderr)
-            return 2
-        inj = args.mfma_scan_inject
-        if inj and args.mfma_scan_formats is not None and inj[1] not in args.mfma_scan_formats:
-            print(f"probe: --mfma-scan-inject into {inj[1]!r}, which --mfma-scan-formats leaves "
-                  f"out", file=sys.stderr)
-            return 2
-    if not args.lane_scan:
-        given = [o for o, v in (("--lane-scan-inject", args.lane_scan_inject),
-                                ("--lane-scan-tests", args.lane_scan_tests),
-                                ("--lane-scan-iters", args.lane_scan_iters),
-                                ("--lane-scan-rounds", args.lane_scan_rounds)) if v is not None]
-        if given:
-            print(f"probe: {given[0]} needs --lane-scan", file=sys.stderr)
-            return 2
-    else:
-        from gpumounter_amd.ops import lanescan as _ls
-
-        if args.lane_scan_iters is not None and not 1 <= args.lane_scan_iters <= _ls.MAX_ITERS:
-            print(f"probe: --lane-scan-iters must be between 1 and {_ls.MAX_ITERS}",
-                  file=sys.stderr)
-            return 2
-        if args.lane_scan_rounds is not None and not 1 <= args.lane_scan_rounds <= 1024:
-            print("probe: --lane-scan-rounds must be between 1 and 1024", file=sys.stderr)
-            return 2
-        inj = args.lane_scan_inject
-        if inj and args.lane_scan_tests is not None and inj[1] not in args.lane_scan_tests:
-            print(f"probe: --lane-scan-inject into {inj[1]!r}, which --lane-scan-tests leaves "
-                  f"out", file=sys.stderr)
-            return 2
-    if not args.cache_scan:
-        given = [o for o, v in (("--cache-scan-inject", args.cache_scan_inject),
-                                ("--cache-scan-poke", args.cache_scan_poke),
-                                ("--cache-scan-tests", args.cache_scan_tests),
-                                ("--cache-scan-iters", args.cache_scan_iters),
-                                ("--cache-scan-rounds", args.cache_scan_rounds)) if v is not None]
-        if given:
-            print(f"probe: {given[0]} needs --cache-scan", file=sys.stderr)
-            return 2
-    else:
-        from gpumounter_amd.ops import cachescan as _cs
-
-        if args.cache_scan_iters is not None and not 1 <= args.cache_scan_iters <= _cs.MAX_ITERS:
-            print(f"probe: --cache-scan-iters must be between 1 and {_cs.MAX_ITERS}",
-                  file=sys.stderr)
-            return 2
-        if args.cache_scan_rounds is not None and not 1 <= args.cache_scan_rounds <= 1024:
-            print("probe: --cache-scan-rounds must be between 1 and 1024", file=sys.stderr)
-            return 2
-        for opt, named in (("--cache-scan-inject", args.cache_scan_inject and
-                            args.cache_scan_inject[1]),
-                           ("--cache-scan-poke", args.cache_scan_poke and args.cache_scan_poke[0])):
-            if named and args.cache_scan_tests is not None and named not in args.cache_scan_tests:
-                print(f"probe: {opt} into {named!r}, which --cache-scan-tests leaves out",
-                      file=sys.stderr)
-                return 2
     if args.bdf:
         bdfs = args.bdf
     else:
@@ -493,15 +436,7 @@ def cmd_probe(args) -> int:
                 r["device"], _memtest_bytes(args.memtest), patterns=args.memtest_patterns,
                 passes=args.memtest_passes, _flip=args.memtest_flip)
             bad |= not r["memtest"]["ok"]
-    if args.cu_scan:
-        from gpumounter_amd.ops import cuscan
-
-        for r in res:
-            r["cuscan"] = cuscan.scan(r["device"], tests=args.cu_scan_tests,
-                                      min_rounds=args.cu_scan_rounds,
-                                      max_rounds=max(16, args.cu_scan_rounds),
-                                      _inject=args.cu_scan_inject)
-            bad |= not r["cuscan"]["ok"]
+    bad |= not _run_scan(cu, args, res)
     if args.host_link is not None:
         from gpumounter_amd.ops import hostlink
 
@@ -523,37 +458,8 @@ def cmd_probe(args) -> int:
                 rounds=args.atomics_rounds or atomics.DEFAULT_ROUNDS,
                 _inject=args.atomics_inject)
             bad |= not r["atomics"]["ok"]
-    if args.mfma_scan:
-        from gpumounter_amd.ops import mfmascan
-
-        rounds = args.mfma_scan_rounds or 1
-        for r in res:
-            r["mfmascan"] = mfmascan.scan(
-                r["device"], formats=args.mfma_scan_formats or mfmascan.ALL_FORMATS,
-                iters=args.mfma_scan_iters or mfmascan.DEFAULT_ITERS, min_rounds=rounds,
-                max_rounds=max(16, rounds), _inject=args.mfma_scan_inject)
-            bad |= not r["mfmascan"]["ok"]
-    if args.lane_scan:
-        from gpumounter_amd.ops import lanescan
-
-        rounds = args.lane_scan_rounds or 1
-        for r in res:
-            r["lanescan"] = lanescan.scan(
-                r["device"], tests=args.lane_scan_tests or lanescan.ALL_TESTS,
-                iters=args.lane_scan_iters or lanescan.DEFAULT_ITERS, min_rounds=rounds,
-                max_rounds=max(16, rounds), _inject=args.lane_scan_inject)
-            bad |= not r["lanescan"]["ok"]
-    if args.cache_scan:
-        from gpumounter_amd.ops import cachescan
-
-        rounds = args.cache_scan_rounds or 1
-        for r in res:
-            r["cachescan"] = cachescan.scan(
-                r["device"], tests=args.cache_scan_tests or cachescan.ALL_TESTS,
-                iters=args.cache_scan_iters or cachescan.DEFAULT_ITERS, min_rounds=rounds,
-                max_rounds=max(16, rounds), _inject=args.cache_scan_inject,
-                _poke=args.cache_scan_poke)
-            bad |= not r["cachescan"]["ok"]
+    for scan in later:
+        bad |= not _run_scan(scan, args, res)
     print(json.dumps(res, indent=2))
     return 1 if bad else 0
 
@@ -718,37 +624,22 @@ def cmd_doctor(args) -> int:
         extra["atomics"] = True
         if args.atomics_inject:
             extra["atomics_inject"] = args.atomics_inject
-    if args.mfma_scan_inject and not args.mfma_scan:
-        print("doctor: --mfma-scan-inject needs --mfma-scan", file=sys.stderr)
-        return 2
-    if args.mfma_scan:
-        extra["mfma_scan"] = True
-        if args.mfma_scan_inject:
-            extra["mfma_scan_inject"] = args.mfma_scan_inject
-    if args.lane_scan_inject and not args.lane_scan:
-        print("doctor: --lane-scan-inject needs --lane-scan", file=sys.stderr)
-        return 2
-    if args.lane_scan:
-        extra["lane_scan"] = True
-        if args.lane_scan_inject:
-            extra["lane_scan_inject"] = args.lane_scan_inject
-    for opt, v in (("--cache-scan-inject", args.cache_scan_inject),
-                   ("--cache-scan-poke", args.cache_scan_poke)):
-        if v and not args.cache_scan:
-            print(f"doctor: {opt} needs --cache-scan", file=sys.stderr)
+    scans = _scans()
+    for scan in scans:
+        error = _scan_usage(scan, args, "doctor")
+        if error:
+            print(error, file=sys.stderr)
             return 2
-    if args.cache_scan:
-        extra["cache_scan"] = True
-        if args.cache_scan_inject:
-            extra["cache_scan_inject"] = args.cache_scan_inject
-        if args.cache_scan_poke:
-            extra["cache_scan_poke"] = args.cache_scan_poke
+        if getattr(args, scan.stem):
+            extra[scan.stem] = True
+            for name in scan.controls:      # the CU scan's are not on this command line
+                if getattr(args, f"{scan.stem}_{name}", None):
+                    extra[f"{scan.stem}_{name}"] = getattr(args, f"{scan.stem}_{name}")
     checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
-                        gpu=(args.gpu or bool(args.burn_in) or bool(memtest_bytes) or args.cu_scan
-                             or args.host_link is not None or args.atomics or args.mfma_scan
-                             or args.lane_scan or args.cache_scan),
-                        burn_in_s=args.burn_in, memtest_bytes=memtest_bytes,
-                        cu_scan=args.cu_scan, **extra)
+                        gpu=(args.gpu or bool(args.burn_in) or bool(memtest_bytes)
+                             or args.host_link is not None or args.atomics
+                             or any(getattr(args, scan.stem) for scan in scans)),
+                        burn_in_s=args.burn_in, memtest_bytes=memtest_bytes, **extra)
     print(doctor.render(checks, args.json))
     return 1 if any(c.status == "fail" for c in checks) else 0
 
@@ -797,17 +688,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--memtest-flip", type=_memtest_arg("parse_flip"), default=None,
                    metavar="OFFSET:MASK",
                    help="negative control: corrupt that word after every fill; the test must fail")
-    p.add_argument("--cu-scan", action="store_true",
-                   help="per-CU self-test of every probed GPU: integer, fp32, MFMA and LDS "
-                        "known-answer tests on every compute unit (exit 1 on any wrong word)")
-    p.add_argument("--cu-scan-tests", type=_cuscan_arg("parse_tests"),
-                   default=("int", "f32", "mfma", "lds"), metavar="a,b,...")
-    p.add_argument("--cu-scan-rounds", type=int, default=1, metavar="N",
-                   help="at least N rounds (a round is one block per CU)")
-    p.add_argument("--cu-scan-inject", type=_cuscan_arg("parse_inject"), default=None,
-                   metavar="ID|any:TEST:THREAD:WORD:MASK",
-                   help="negative control: flip that signature word on that CU; the scan must "
-                        "name it")
+    cu, *later = _scans()
+    _add_probe_scan(p, cu)
     _add_hostlink_size(p, "host link (PCIe) test of every probed GPU over SIZE bytes of pinned "
                           "host memory per buffer (default 256M): checked transfers in both "
                           "directions by the copy engines and by kernels (exit 1 on any bad word)")
@@ -833,36 +715,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="blocks of 256 threads, 1..4096 (default: one per CU)")
     p.add_argument("--atomics-rounds", type=int, default=None, metavar="N",
                    help="hand-off rounds, 1..64 (default 8)")
-    _add_mfmascan(p, "per-CU matrix-core format scan of every probed GPU: bit-exact MFMAs in "
-                     "f16, fp8, bf8, i8, f32, f64 and the block-scaled fp8, bf8, fp6, bf6 and fp4 "
-                     "forms on every compute unit (exit 1 on any wrong word)")
-    p.add_argument("--mfma-scan-formats", type=_mfmascan_arg("parse_formats"), default=None,
-                   metavar="a,b,...",
-                   help="of f16,fp8,bf8,i8,f32,f64,mxfp8,mxbf8,mxfp6,mxbf6,mxfp4 (default: all)")
-    p.add_argument("--mfma-scan-iters", type=int, default=None, metavar="N",
-                   help="dependent MFMAs per wave and format, 1..63 (default 16)")
-    p.add_argument("--mfma-scan-rounds", type=int, default=None, metavar="N",
-                   help="at least N rounds (a round is one block per CU)")
-    _add_lanescan(p, "per-CU register, lane and scalar-unit scan of every probed GPU: bit-exact "
-                     "cross-lane moves, a register-file march, a scalar chain, transcendentals at "
-                     "exact points, fp64 and packed arithmetic on every compute unit (exit 1 on "
-                     "any wrong word)")
-    p.add_argument("--lane-scan-tests", type=_lanescan_arg("parse_tests"), default=None,
-                   metavar="a,b,...", help="of xlane,regfile,salu,trans,f64,packed (default: all)")
-    p.add_argument("--lane-scan-iters", type=int, default=None, metavar="N",
-                   help="units of work per test, 1..63 (default 16)")
-    p.add_argument("--lane-scan-rounds", type=int, default=None, metavar="N",
-                   help="at least N rounds (a round is one block per CU)")
-    _add_cachescan(p, "per-CU cache scan of every probed GPU: a march served by the L2, hit and "
-                      "replacement passes through the vector L1, a pointer chase through the "
-                      "scalar data cache and a body larger than the instruction cache on every "
-                      "compute unit (exit 1 on any wrong word)")
-    p.add_argument("--cache-scan-tests", type=_cachescan_arg("parse_tests"), default=None,
-                   metavar="a,b,...", help="of l2,l1,scalar,icache (default: all)")
-    p.add_argument("--cache-scan-iters", type=int, default=None, metavar="N",
-                   help="units of work per test, 1..63 (default 4)")
-    p.add_argument("--cache-scan-rounds", type=int, default=None, metavar="N",
-                   help="at least N rounds (a round is one block per CU)")
+    for scan in later:
+        _add_probe_scan(p, scan)
     p.set_defaults(fn=cmd_probe)
     for name, fn in (("add", cmd_add), ("remove", cmd_remove), ("status", cmd_status)):
         p = sub.add_parser(name)
@@ -900,17 +754,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --gpu: sustained bit-checked GEMM load per GPU")
     _add_memtest_size(p, "with --gpu: HBM pattern test over SIZE bytes per GPU (default: 90 %% of "
                          "its free memory)")
-    p.add_argument("--cu-scan", action="store_true",
-                   help="with --gpu: per-CU self-test of every GPU; a failing CU is named")
+    _add_doctor_scan(p, cu)
     _add_hostlink_size(p, "with --gpu: host link (PCIe) test of every GPU over SIZE bytes of "
                           "pinned host memory per buffer (default 256M)")
     _add_atomics(p, "with --gpu: cross-XCC atomics and coherence test of every GPU")
-    _add_mfmascan(p, "with --gpu: per-CU matrix-core format scan of every GPU; a failing CU "
-                     "is named with the format")
-    _add_lanescan(p, "with --gpu: per-CU register, lane and scalar-unit scan of every GPU; a "
-                     "failing CU is named with the test")
-    _add_cachescan(p, "with --gpu: per-CU cache scan (vector L1, L2, scalar and instruction "
-                      "caches) of every GPU; a failing CU is named with the test")
+    for scan in later:
+        _add_doctor_scan(p, scan)
     p.set_defaults(fn=cmd_doctor)
     p = sub.add_parser("bpf-dump")
     p.add_argument("--allow", action="append", default=[])

@@ -35,11 +35,11 @@ missing ``libgm_probe.so`` or a HIP failure raises.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Iterable, Tuple
+from typing import Dict
 
 from gpumounter_amd import _native
-from gpumounter_amd.ops import cuscan
-from gpumounter_amd.ops.cuscan import ANY, DEFAULT_SEED, MAX_ROUNDS, THREADS, WORDS
+from gpumounter_amd.ops import cuframe
+from gpumounter_amd.ops.cuframe import ANY, DEFAULT_SEED, _ref
 from gpumounter_amd.ops.probe import ProbeError, _check
 
 TESTS = {"l2": 1, "l1": 2, "scalar": 4, "icache": 8}
@@ -56,58 +56,21 @@ __all__ = ["TESTS", "ALL_TESTS", "DEFAULT_ITERS", "MAX_ITERS", "ANY", "ProbeErro
            "geometry", "describe_failed"]
 
 
-def bit_of(test) -> int:
-    """The bit of one test, given by name or by bit."""
-    if isinstance(test, str) and test in TESTS:
-        return TESTS[test]
-    if isinstance(test, int) and not isinstance(test, bool) and test in TEST_NAMES:
-        return test
-    raise ProbeError(f"unknown cache-scan test {test!r} (one of {', '.join(TESTS)})")
-
-
-def mask_of(tests: Iterable) -> int:
-    if isinstance(tests, (str, int)):
-        tests = (tests,)
-    mask = 0
-    for t in tests:
-        mask |= bit_of(t)
-    if not mask:
-        raise ProbeError("cache-scan needs at least one test")
-    return mask
-
-
-def parse_tests(text) -> Tuple[str, ...]:
-    """``"l2,icache"`` → ("l2", "icache"); every name is checked."""
-    names = tuple(t.strip() for t in str(text).split(",") if t.strip())
-    mask_of(names)
-    return names
-
-
-def _int(v, lo: int, hi: int, what: str) -> int:
-    if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
-        raise ProbeError(f"cache-scan: {what} must be an integer in [{lo}, {hi}], got {v!r}")
-    return v
-
-
-def _inject_arg(inject, mask: int):
-    """(id or "any", test, thread, word, xor mask) → the C struct; None stays None."""
-    if inject is None:
-        return None
-    try:
-        cu_id, test, thread, word, xor = inject
-    except (TypeError, ValueError):
-        raise ProbeError(f"cache-scan: injection {inject!r} is not (id, test, thread, word, "
-                         f"mask)") from None
-    bit = bit_of(test)
-    if not bit & mask:
-        raise ProbeError(f"cache-scan: injection into {TEST_NAMES[bit]!r}, which is not run")
-    if cu_id != ANY:
-        cuscan.decode_id(cu_id)
-    _int(thread, 0, THREADS - 1, "injection thread")
-    _int(word, 0, WORDS - 1, "injection word")
-    _int(xor, 1, 0xFFFFFFFF, "injection mask")
-    return _native.CuscanInject(_native.CUSCAN_ANY if cu_id == ANY else cu_id, bit, thread, word,
-                                xor)
+SCAN = cuframe.Scan(
+    label="cache-scan", key="cachescan", bits=TESTS, selection="tests",
+    default_iters=DEFAULT_ITERS, max_iters=MAX_ITERS, title="per-CU cache scan",
+    covers=" (vector L1, L2, scalar and instruction caches)",
+    does="a march served by the L2, hit and replacement passes through the vector L1, a pointer "
+         "chase through the scalar data cache and a body larger than the instruction cache",
+    flips="signature word of that test", iters_unit="units of work per test",
+    more_controls={"poke": (
+        "TEST:WORD_OFFSET:MASK",
+        "negative control: flip that word of the test's data (l2, l1: of every block's segment "
+        "after the fill; scalar: of the table); the test must find it", "data poke")})
+bit_of, mask_of, parse_tests, parse_inject = (SCAN.bit_of, SCAN.mask_of, SCAN.parse_list,
+                                              SCAN.parse_inject)
+describe_failed = SCAN.describe_failed
+_int = SCAN.check_int
 
 
 def _poke_arg(poke, mask: int):
@@ -130,22 +93,6 @@ def _poke_arg(poke, mask: int):
     return _native.CachescanPoke(bit, offset, xor)
 
 
-def parse_inject(text):
-    """``"ID|any:TEST:THREAD:WORD:MASK"`` (integers as Python literals, e.g.
-    ``0x123:l1:130:2:0x10000``) → (id or "any", test name, thread, word, mask)."""
-    parts = [p.strip() for p in str(text).split(":")]
-    if len(parts) != 5:
-        raise ProbeError(f"cache-scan: cannot read {text!r} as ID|any:TEST:THREAD:WORD:MASK")
-    try:
-        cu_id = ANY if parts[0].lower() == ANY else int(parts[0], 0)
-        thread, word, xor = (int(p, 0) for p in parts[2:])
-    except ValueError:
-        raise ProbeError(f"cache-scan: {text!r} holds something that is not an integer") from None
-    inj = (cu_id, TEST_NAMES[bit_of(parts[1])], thread, word, xor)
-    _inject_arg(inj, TESTS[inj[1]])
-    return inj
-
-
 def parse_poke(text):
     """``"TEST:WORD_OFFSET:MASK"`` (integers as Python literals, e.g. ``l1:4099:0x10``) →
     (test name, word offset, mask)."""
@@ -161,48 +108,18 @@ def parse_poke(text):
     return poke
 
 
-def _ref(arg):
-    return C.byref(arg) if arg is not None else None
-
-
 def expected(test, seed: int = DEFAULT_SEED, iters: int = DEFAULT_ITERS, poke=None):
     """numpy uint32[256, 4]: word i of thread t of ``test``'s signature, in a run with ``poke``
     (a poke of another test leaves it alone). Host only, no GPU."""
-    import numpy as np
-
-    bit = bit_of(test)
-    _int(seed, 0, (1 << 64) - 1, "seed"), _int(iters, 1, MAX_ITERS, "iters")
-    pk = _poke_arg(poke, TESTS["l2"] | TESTS["l1"] | TESTS["scalar"] | TESTS["icache"])
-    out = np.empty(THREADS * WORDS, dtype=np.uint32)
-    _check(_native.probe().gm_probe_cachescan_expected(
-        bit, seed, iters, _ref(pk), out.ctypes.data_as(C.POINTER(C.c_uint32))),
-        "cache-scan expected")
-    return out.reshape(THREADS, WORDS)
+    return SCAN.expected(test, seed, iters,
+                         lambda bit: (_ref(_poke_arg(poke, mask_of(ALL_TESTS))),))
 
 
 def signature(test, seed: int = DEFAULT_SEED, iters: int = DEFAULT_ITERS, stream=None, poke=None):
     """One block of the scan's device code on the current device, on an arena of its own:
     (uint32[256, 4] raw signature, where), ``where`` as
     :func:`gpumounter_amd.ops.cuscan.signature` gives it. ``poke`` must name ``test``."""
-    bit = bit_of(test)
-    _int(seed, 0, (1 << 64) - 1, "seed"), _int(iters, 1, MAX_ITERS, "iters")
-    pk = _poke_arg(poke, bit)
-    import numpy as np
-    import torch
-
-    out = torch.zeros(THREADS * WORDS, dtype=torch.int32, device="cuda")
-    where = torch.full((5,), -1, dtype=torch.int32, device="cuda")
-    s = stream if stream is not None else torch.cuda.current_stream(out.device)
-    if stream is not None:
-        s.wait_stream(torch.cuda.current_stream(out.device))   # out and where are filled there
-    with torch.cuda.device(out.device):
-        _check(_native.probe().gm_probe_cachescan_signature(
-            bit, seed, iters, _ref(pk), out.data_ptr(), where.data_ptr(),
-            C.c_void_p(s.cuda_stream)), "cache-scan signature")
-    s.synchronize()
-    w = [int(v) & 0xFFFFFFFF for v in where.cpu().tolist()]
-    sig = out.cpu().numpy().view(np.uint32).reshape(THREADS, WORDS)
-    return sig, {"id": w[0], **cuscan.decode_id(w[0] & (_native.CUSCAN_IDS - 1)), "simds": w[1:]}
+    return SCAN.signature(test, seed, iters, stream, lambda bit: (_ref(_poke_arg(poke, bit)),))
 
 
 def decode_timing(mask: int, timing) -> Dict:
@@ -223,23 +140,10 @@ def scan(dev: int, tests=ALL_TESTS, iters: int = DEFAULT_ITERS, seed: int = DEFA
     in a record), plus ``timing`` (:func:`decode_timing`; shader-clock counts, reported and never
     judged). ``_inject=(id or "any", test, thread, word, mask)`` and ``_poke=(test, word offset,
     mask)`` are the negative controls."""
-    mask = mask_of(tests)
-    _int(iters, 1, MAX_ITERS, "iters")
-    _int(dev, 0, (1 << 31) - 1, "device")
-    _int(seed, 0, (1 << 64) - 1, "seed")
-    _int(min_rounds, 1, MAX_ROUNDS, "min_rounds")
-    _int(max_rounds, min_rounds, MAX_ROUNDS, "max_rounds (at least min_rounds)")
-    inj = _inject_arg(_inject, mask)
-    pk = _poke_arg(_poke, mask)
-    res = _native.CuscanResult()
-    cus = (_native.CuscanCu * _native.CUSCAN_IDS)()
-    n = C.c_int(0)
     timing = _native.CachescanTiming()
-    _check(_native.probe().gm_probe_cachescan(
-        dev, mask, iters, seed, min_rounds, max_rounds, _ref(inj), _ref(pk), C.byref(res), cus,
-        _native.CUSCAN_IDS, C.byref(n), C.byref(timing)), "cache-scan")
-    out = cuscan.decode_result(dev, mask, iters, res, cus, n.value, TESTS, "tests")
-    out["timing"] = decode_timing(mask, timing)
+    out = SCAN.scan(dev, tests, iters, seed, min_rounds, max_rounds, _inject,
+                    lambda mask: (_ref(_poke_arg(_poke, mask)),), (C.byref(timing),))
+    out["timing"] = decode_timing(mask_of(tests), timing)
     return out
 
 
@@ -263,9 +167,3 @@ def geometry() -> Dict[str, int]:
            "cache-scan geometry")
     return dict(zip(("seg_bytes", "l1_hit_bytes", "table_bytes", "icache_steps"),
                     (x.value for x in v)))
-
-
-def describe_failed(result: Dict) -> str:
-    """One line naming the failed units of a :func:`scan` result as the CU scan names them, with
-    the tests that failed there, for ``doctor``."""
-    return cuscan.describe_failed(result, "tests")

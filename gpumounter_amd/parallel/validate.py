@@ -46,6 +46,9 @@ import os
 import sys
 from typing import Dict, List
 
+from gpumounter_amd.ops import cuframe
+from gpumounter_amd.ops.probe import ProbeError
+
 
 def _rank_main(rank: int, world: int, cpu: bool, numel: int, out_dir: str) -> None:
     import torch
@@ -86,6 +89,20 @@ def run_allreduce(world: int, cpu: bool, numel: int) -> List[Dict]:
     return res
 
 
+def _run_scan(scan, args, controls: Dict, world: int, report: Dict) -> None:
+    """One per-CU scan, if it was asked for, on every GPU at once, booked under its key."""
+    if not getattr(args, scan.stem):
+        return
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(max_workers=world) as ex:
+        res = list(ex.map(lambda d: scan.run(d, **controls[scan.key]), range(world)))
+    for r in res:
+        del r["per_cu"]                   # one line per CU and GPU; "failed" names the bad ones
+    report[scan.key] = res
+    report["ok"] &= all(r["ok"] for r in res)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="gpumounter_amd.parallel.validate")
     ap.add_argument("--cpu-ranks", type=int, default=0,
@@ -97,8 +114,9 @@ def main(argv=None) -> int:
     ap.add_argument("--memtest", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the HBM pattern test on every GPU at once over SIZE bytes each "
                          "(64M, 8G; default: 90 %% of the free memory)")
+    cu, *later = cuframe.registry()   # the CU scan: before the host-link and atomics tests
     ap.add_argument("--cu-scan", action="store_true",
-                    help="then the per-CU self-test on every GPU at once")
+                    help=f"then the {cu.title} on every GPU at once")
     ap.add_argument("--host-link", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the host link (PCIe) test on every GPU at once over SIZE bytes of "
                          "pinned host memory per buffer (default 256M)")
@@ -106,53 +124,25 @@ def main(argv=None) -> int:
                     help="then the cross-XCC atomics and coherence test on every GPU at once")
     ap.add_argument("--atomics-inject", default=None, metavar="TEST:...",
                     help="its negative control (see probe --atomics-inject); needs --atomics")
-    ap.add_argument("--mfma-scan", action="store_true",
-                    help="then the per-CU matrix-core format scan on every GPU at once")
-    ap.add_argument("--mfma-scan-inject", default=None,
-                    metavar="ID|any:FORMAT:THREAD:WORD:MASK",
-                    help="its negative control (see probe --mfma-scan-inject); needs --mfma-scan")
-    ap.add_argument("--lane-scan", action="store_true",
-                    help="then the per-CU register, lane and scalar-unit scan on every GPU at once")
-    ap.add_argument("--lane-scan-inject", default=None, metavar="ID|any:TEST:THREAD:WORD:MASK",
-                    help="its negative control (see probe --lane-scan-inject); needs --lane-scan")
-    ap.add_argument("--cache-scan", action="store_true",
-                    help="then the per-CU cache scan (vector L1, L2, scalar and instruction "
-                         "caches) on every GPU at once")
-    ap.add_argument("--cache-scan-inject", default=None, metavar="ID|any:TEST:THREAD:WORD:MASK",
-                    help="its negative control (see probe --cache-scan-inject); needs --cache-scan")
-    ap.add_argument("--cache-scan-poke", default=None, metavar="TEST:WORD_OFFSET:MASK",
-                    help="its data poke (see probe --cache-scan-poke); needs --cache-scan")
+    for scan in later:
+        ap.add_argument(f"--{scan.label}", action="store_true",
+                        help=f"then the {scan.title}{scan.covers} on every GPU at once")
+        for name, (metavar, _, what) in scan.controls.items():
+            ap.add_argument(f"--{scan.label}-{name}", default=None, metavar=metavar,
+                            help=f"its {what} (see probe --{scan.label}-{name}); needs "
+                                 f"--{scan.label}")
     args = ap.parse_args(argv)
-    cache_scan_inject = cache_scan_poke = None
-    if args.cache_scan_inject is not None or args.cache_scan_poke is not None:
-        from gpumounter_amd.ops import cachescan
-        if not args.cache_scan:
-            ap.error(("--cache-scan-inject" if args.cache_scan_inject is not None
-                      else "--cache-scan-poke") + " needs --cache-scan")
+    controls: Dict = {cu.key: {}}     # scan → the keyword arguments of its negative controls
+    for scan in reversed(later):      # errors have always been reported for the last scan first
+        texts = {name: getattr(args, f"{scan.stem}_{name}") for name in scan.controls}
+        given = [name for name, text in texts.items() if text is not None]
+        if given and not getattr(args, scan.stem):
+            ap.error(f"--{scan.label}-{given[0]} needs --{scan.label}")
         try:
-            if args.cache_scan_inject is not None:
-                cache_scan_inject = cachescan.parse_inject(args.cache_scan_inject)
-            if args.cache_scan_poke is not None:
-                cache_scan_poke = cachescan.parse_poke(args.cache_scan_poke)
-        except cachescan.ProbeError as e:
-            ap.error(str(e))
-    lane_scan_inject = None
-    if args.lane_scan_inject is not None:
-        from gpumounter_amd.ops import lanescan
-        if not args.lane_scan:
-            ap.error("--lane-scan-inject needs --lane-scan")
-        try:
-            lane_scan_inject = lanescan.parse_inject(args.lane_scan_inject)
-        except lanescan.ProbeError as e:
-            ap.error(str(e))
-    mfma_scan_inject = None
-    if args.mfma_scan_inject is not None:
-        from gpumounter_amd.ops import mfmascan
-        if not args.mfma_scan:
-            ap.error("--mfma-scan-inject needs --mfma-scan")
-        try:
-            mfma_scan_inject = mfmascan.parse_inject(args.mfma_scan_inject)
-        except mfmascan.ProbeError as e:
+            controls[scan.key] = {
+                f"_{name}": text if text is None else getattr(scan.module, f"parse_{name}")(text)
+                for name, text in texts.items()}
+        except ProbeError as e:
             ap.error(str(e))
     atomics_inject = None
     if args.atomics_inject is not None:
@@ -224,17 +214,8 @@ def main(argv=None) -> int:
             mt = list(ex.map(lambda d: memtest.memtest(d, memtest_bytes), range(world)))
         report["memtest"] = mt
         report["ok"] &= all(m["ok"] for m in mt)
-    if args.cu_scan and not args.cpu_ranks:
-        from concurrent.futures import ThreadPoolExecutor
-
-        from gpumounter_amd.ops import cuscan
-
-        with ThreadPoolExecutor(max_workers=world) as ex:
-            cs = list(ex.map(cuscan.scan, range(world)))
-        for c in cs:
-            del c["per_cu"]               # one line per CU and GPU; "failed" names the bad ones
-        report["cuscan"] = cs
-        report["ok"] &= all(c["ok"] for c in cs)
+    if not args.cpu_ranks:
+        _run_scan(cu, args, controls, world, report)
     if args.host_link is not None and not args.cpu_ranks:
         from concurrent.futures import ThreadPoolExecutor
 
@@ -257,40 +238,8 @@ def main(argv=None) -> int:
             #                               "first_errors" names the XCCs then
         report["atomics"] = at
         report["ok"] &= all(a["ok"] for a in at)
-    if args.mfma_scan and not args.cpu_ranks:
-        from concurrent.futures import ThreadPoolExecutor
-
-        from gpumounter_amd.ops import mfmascan
-
-        with ThreadPoolExecutor(max_workers=world) as ex:
-            ms = list(ex.map(lambda d: mfmascan.scan(d, _inject=mfma_scan_inject), range(world)))
-        for m in ms:
-            del m["per_cu"]               # as for the CU scan: "failed" names the bad ones
-        report["mfmascan"] = ms
-        report["ok"] &= all(m["ok"] for m in ms)
-    if args.lane_scan and not args.cpu_ranks:
-        from concurrent.futures import ThreadPoolExecutor
-
-        from gpumounter_amd.ops import lanescan
-
-        with ThreadPoolExecutor(max_workers=world) as ex:
-            ls = list(ex.map(lambda d: lanescan.scan(d, _inject=lane_scan_inject), range(world)))
-        for m in ls:
-            del m["per_cu"]               # as for the CU scan: "failed" names the bad ones
-        report["lanescan"] = ls
-        report["ok"] &= all(m["ok"] for m in ls)
-    if args.cache_scan and not args.cpu_ranks:
-        from concurrent.futures import ThreadPoolExecutor
-
-        from gpumounter_amd.ops import cachescan
-
-        with ThreadPoolExecutor(max_workers=world) as ex:
-            cs = list(ex.map(lambda d: cachescan.scan(d, _inject=cache_scan_inject,
-                                                      _poke=cache_scan_poke), range(world)))
-        for m in cs:
-            del m["per_cu"]               # as for the CU scan: "failed" names the bad ones
-        report["cachescan"] = cs
-        report["ok"] &= all(m["ok"] for m in cs)
+    for scan in later if not args.cpu_ranks else ():
+        _run_scan(scan, args, controls, world, report)
     print(json.dumps(report))
     return 0 if report["ok"] else 1
 

@@ -280,6 +280,22 @@ async def _check_priority(cfg, kube) -> List[Check]:
     return out
 
 
+def _scan_segment(scan, dev: int, given) -> tuple:
+    """(what one per-CU scan adds to a GPU's detail line, whether it fails the check); ``given``
+    holds check_gpus' parameters: the scan runs only if its switch is on."""
+    if not given[scan.stem]:
+        return "", False
+    r = scan.run(dev, **{f"_{name}": given[f"{scan.stem}_{name}"] for name in scan.controls})
+    counted = "" if scan.plain_cli else f" {len(r[scan.selection])} {scan.selection}"
+    text = (f", {scan.label}{counted} {r['cus_seen']}/{r['cus_expected']} CUs in {r['rounds']} "
+            f"round(s) {r['kernel_ms']:.2f} ms {r['words_in_error']} wrong words")
+    if not r["complete"]:
+        text += " (incomplete: not every CU was reached)"
+    if not r["ok"]:
+        text += f", failed: {scan.describe_failed(r)}"
+    return text, not r["ok"]
+
+
 def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                memtest_flip=None, burn_in_flip=None, cu_scan: bool = False,
                cu_scan_inject=None, host_link_bytes: int = 0,
@@ -315,9 +331,11 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     L1, L2, scalar and instruction caches), failed, named and stated in the same way;
     ``cache_scan_inject`` and ``cache_scan_poke`` are its negative controls. A GPU that fails here
     should not be handed out."""
+    given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.hw.inventory import Inventory
-    from gpumounter_amd.ops import probe
+    from gpumounter_amd.ops import cuframe, probe
 
+    cu, *later = cuframe.registry()   # the CU scan: before the host-link and atomics tests
     try:
         n = probe.device_count()
     except Exception as e:  # noqa: BLE001 - no HIP runtime / driver
@@ -354,17 +372,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                 detail += (f", memtest {m['bytes'] / 2**30:.2f} GiB {m['read_gbps']:.0f} / "
                            f"{m['write_gbps']:.0f} GB/s {m['errors']} bad words")
                 status = status if m["ok"] else "fail"
-            if cu_scan:
-                from gpumounter_amd.ops import cuscan
-
-                c = cuscan.scan(d, _inject=cu_scan_inject)
-                detail += (f", cu-scan {c['cus_seen']}/{c['cus_expected']} CUs in {c['rounds']} "
-                           f"round(s) {c['kernel_ms']:.2f} ms {c['words_in_error']} wrong words")
-                if not c["complete"]:
-                    detail += " (incomplete: not every CU was reached)"
-                if not c["ok"]:
-                    detail += f", failed: {cuscan.describe_failed(c)}"
-                    status = "fail"
+            text, failed = _scan_segment(cu, d, given)
+            detail, status = detail + text, "fail" if failed else status
             if host_link_bytes:
                 from gpumounter_amd.ops import hostlink
 
@@ -400,42 +409,9 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                 elif a["handoff_vacuous"]:
                     detail += ", no hand-off was seen within the budget: it proved nothing"
                     status = "warn" if status == "ok" else status
-            if mfma_scan:
-                from gpumounter_amd.ops import mfmascan
-
-                m = mfmascan.scan(d, _inject=mfma_scan_inject)
-                detail += (f", mfma-scan {len(m['formats'])} formats {m['cus_seen']}/"
-                           f"{m['cus_expected']} CUs in {m['rounds']} round(s) "
-                           f"{m['kernel_ms']:.2f} ms {m['words_in_error']} wrong words")
-                if not m["complete"]:
-                    detail += " (incomplete: not every CU was reached)"
-                if not m["ok"]:
-                    detail += f", failed: {mfmascan.describe_failed(m)}"
-                    status = "fail"
-            if lane_scan:
-                from gpumounter_amd.ops import lanescan
-
-                m = lanescan.scan(d, _inject=lane_scan_inject)
-                detail += (f", lane-scan {len(m['tests'])} tests {m['cus_seen']}/"
-                           f"{m['cus_expected']} CUs in {m['rounds']} round(s) "
-                           f"{m['kernel_ms']:.2f} ms {m['words_in_error']} wrong words")
-                if not m["complete"]:
-                    detail += " (incomplete: not every CU was reached)"
-                if not m["ok"]:
-                    detail += f", failed: {lanescan.describe_failed(m)}"
-                    status = "fail"
-            if cache_scan:
-                from gpumounter_amd.ops import cachescan
-
-                m = cachescan.scan(d, _inject=cache_scan_inject, _poke=cache_scan_poke)
-                detail += (f", cache-scan {len(m['tests'])} tests {m['cus_seen']}/"
-                           f"{m['cus_expected']} CUs in {m['rounds']} round(s) "
-                           f"{m['kernel_ms']:.2f} ms {m['words_in_error']} wrong words")
-                if not m["complete"]:
-                    detail += " (incomplete: not every CU was reached)"
-                if not m["ok"]:
-                    detail += f", failed: {cachescan.describe_failed(m)}"
-                    status = "fail"
+            for scan in later:
+                text, failed = _scan_segment(scan, d, given)
+                detail, status = detail + text, "fail" if failed else status
             out.append(Check(f"gpu{d}", status, detail))
         except Exception as e:  # noqa: BLE001 - a faulting GPU is exactly what this finds
             out.append(Check(f"gpu{d}", "fail", f"probe failed: {e}"))
@@ -451,30 +427,25 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         mfma_scan: bool = False, mfma_scan_inject=None, lane_scan: bool = False,
         lane_scan_inject=None, cache_scan: bool = False, cache_scan_inject=None,
         cache_scan_poke=None) -> List[Check]:
+    given = dict(locals())            # the scans' switches and controls, by parameter name
+    from gpumounter_amd.ops import cuframe
+
     checks = check_inventory(cfg) + check_cgroup(cfg) + check_devnodes(cfg) + \
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
-        extra = {"cu_scan": True} if cu_scan else {}
+        extra = {}
         if host_link_bytes:
             extra["host_link_bytes"] = host_link_bytes
         if atomics:
             extra["atomics"] = True
             if atomics_inject is not None:
                 extra["atomics_inject"] = atomics_inject
-        if mfma_scan:
-            extra["mfma_scan"] = True
-            if mfma_scan_inject is not None:
-                extra["mfma_scan_inject"] = mfma_scan_inject
-        if lane_scan:
-            extra["lane_scan"] = True
-            if lane_scan_inject is not None:
-                extra["lane_scan_inject"] = lane_scan_inject
-        if cache_scan:
-            extra["cache_scan"] = True
-            if cache_scan_inject is not None:
-                extra["cache_scan_inject"] = cache_scan_inject
-            if cache_scan_poke is not None:
-                extra["cache_scan_poke"] = cache_scan_poke
+        for scan in cuframe.registry():
+            if given[scan.stem]:
+                extra[scan.stem] = True
+                for name in scan.controls:     # the CU scan's are not among the parameters
+                    if given.get(f"{scan.stem}_{name}") is not None:
+                        extra[f"{scan.stem}_{name}"] = given[f"{scan.stem}_{name}"]
         checks += check_gpus(cfg, burn_in_s, memtest_bytes=memtest_bytes, **extra)
     if not skip_cluster:
         async def both():

@@ -275,19 +275,13 @@ __global__ __launch_bounds__(GM_CUSCAN_THREADS) void k_cachescan(
   book_block<kCompare>(lds, at, failed, bad, tab, where_out);
 }
 
-bool one_test_bit(uint32_t t) {
-  return t != 0 && (t & (t - 1)) == 0 && (t & ~(uint32_t)GM_CACHESCAN_ALL) == 0;
-}
+bool iters_ok(uint32_t, uint32_t iters) { return iters >= 1 && iters <= GM_CACHESCAN_MAX_ITERS; }
 
-bool iters_ok(uint32_t iters) { return iters >= 1 && iters <= GM_CACHESCAN_MAX_ITERS; }
-
-bool inject_ok(const gm_cuscan_inject_t* in, uint32_t tests) {
-  return one_test_bit(in->test) && inject_fields_ok(in, tests);
-}
+constexpr ScanArgs kArgs = {GM_CACHESCAN_ALL, iters_ok};
 
 // a poke of one selected test that has data, inside that data
 bool poke_ok(const gm_cachescan_poke_t* pk, uint32_t tests) {
-  if (!one_test_bit(pk->test) || !(pk->test & tests) || pk->mask == 0) return false;
+  if (!one_bit_ok(kArgs, pk->test) || !(pk->test & tests) || pk->mask == 0) return false;
   if (pk->test == GM_CACHESCAN_ICACHE) return false;
   return pk->word_offset <
          (pk->test == GM_CACHESCAN_SCALAR ? GM_CACHESCAN_TABLE_WORDS : GM_CACHESCAN_SEG_WORDS);
@@ -341,7 +335,7 @@ extern "C" {
 
 int gm_probe_cachescan_expected(uint32_t test, uint64_t seed, uint32_t iters,
                                 const gm_cachescan_poke_t* poke, uint32_t* out) {
-  if (!one_test_bit(test) || !iters_ok(iters) || !out) return (int)hipErrorInvalidValue;
+  if (!one_test_ok(kArgs, test, iters) || !out) return (int)hipErrorInvalidValue;
   // a poke of another test is a legal run in which this test's table is the clean one
   if (poke && !poke_ok(poke, GM_CACHESCAN_ALL)) return (int)hipErrorInvalidValue;
   expected_of(test, seed, iters, poke, out);
@@ -361,13 +355,10 @@ int gm_probe_cachescan_geometry(uint32_t* seg_bytes, uint32_t* l1_hit_bytes, uin
 int gm_probe_cachescan_signature(uint32_t test, uint64_t seed, uint32_t iters,
                                  const gm_cachescan_poke_t* poke, uint32_t* dev_out,
                                  uint32_t* dev_where, void* stream) {
-  if (!one_test_bit(test) || !iters_ok(iters) || !dev_out || ((uintptr_t)dev_out & 15) ||
-      !dev_where || ((uintptr_t)dev_where & 3) || (poke && !poke_ok(poke, test)))
+  if (!one_test_ok(kArgs, test, iters) || !signature_out_ok(dev_out, dev_where) ||
+      (poke && !poke_ok(poke, test)))
     return (int)hipErrorInvalidValue;
-  Params p{};
-  p.seed = seed;
-  p.tests = test;
-  p.iters = iters;
+  const Params p = params_of(seed, test, iters);
   Run run;
   if (int e = run.alloc(1, seed, poke, (hipStream_t)stream)) return e;
   hipLaunchKernelGGL(k_cachescan<false>, dim3(1), dim3(GM_CUSCAN_THREADS), 0, (hipStream_t)stream, p,
@@ -383,19 +374,12 @@ int gm_probe_cachescan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t se
                        int max_rounds, const gm_cuscan_inject_t* inject,
                        const gm_cachescan_poke_t* poke, gm_cuscan_result_t* out, gm_cuscan_cu_t* cus,
                        int cus_cap, int* n_cus, gm_cachescan_timing_t* timing) {
-  if (!out) return (int)hipErrorInvalidValue;
-  memset(out, 0, sizeof(*out));
-  if (timing) memset(timing, 0, sizeof(*timing));
-  if (n_cus) *n_cus = 0;
-  if (tests_mask == 0 || (tests_mask & ~(uint32_t)GM_CACHESCAN_ALL) || !iters_ok(iters) ||
-      !rounds_ok(min_rounds, max_rounds, cus, cus_cap) || (inject && !inject_ok(inject, tests_mask)) ||
+  if (out && timing) memset(timing, 0, sizeof(*timing));
+  if (!scan_args_ok(kArgs, tests_mask, iters, min_rounds, max_rounds, inject, out, cus, cus_cap,
+                    n_cus) ||
       (poke && !poke_ok(poke, tests_mask)))
     return (int)hipErrorInvalidValue;
-  Params p{};
-  p.seed = seed;
-  p.tests = tests_mask;
-  p.iters = iters;
-  if (inject) p.inj = *inject;
+  const Params p = params_of(seed, tests_mask, iters, inject);
   const gm_cachescan_poke_t pk = poke ? *poke : gm_cachescan_poke_t{};
   DeviceGuard g(dev);  // the buffers below are this device's, from the first launch to the read
   if (!g.ok) return (int)hipErrorInvalidDevice;

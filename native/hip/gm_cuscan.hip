@@ -99,61 +99,41 @@ __global__ __launch_bounds__(GM_CUSCAN_THREADS) void k_cuscan(Params p,
   book_block<kCompare>(lds, at, failed, bad, tab, where_out);
 }
 
-bool one_test(uint32_t t) {
-  return t == GM_CUSCAN_VALU_INT || t == GM_CUSCAN_VALU_F32 || t == GM_CUSCAN_MFMA ||
-         t == GM_CUSCAN_LDS;
-}
-
 bool iters_ok(uint32_t tests, uint32_t iters) {
   if (iters == 0 || iters > GM_CUSCAN_MAX_ITERS) return false;
   return !(tests & GM_CUSCAN_MFMA) || iters <= GM_CUSCAN_MFMA_MAX_ITERS;
 }
 
-bool inject_ok(const gm_cuscan_inject_t* in, uint32_t tests) {
-  return one_test(in->test) && inject_fields_ok(in, tests);
-}
+constexpr ScanArgs kArgs = {GM_CUSCAN_ALL, iters_ok};
 
 }  // namespace
 
 extern "C" {
 
 int gm_probe_cuscan_expected(uint32_t test, uint64_t seed, uint32_t iters, uint32_t* out) {
-  if (!one_test(test) || !iters_ok(test, iters) || !out) return (int)hipErrorInvalidValue;
+  if (!one_test_ok(kArgs, test, iters) || !out) return (int)hipErrorInvalidValue;
   gm_cuscan_expected_host(test, seed, iters, out);
   return 0;
 }
 
 int gm_probe_cuscan_signature(uint32_t test, uint64_t seed, uint32_t iters, uint32_t* dev_out,
                               uint32_t* dev_where, void* stream) {
-  if (!one_test(test) || !iters_ok(test, iters) || !dev_out || ((uintptr_t)dev_out & 15) ||
-      !dev_where || ((uintptr_t)dev_where & 3))
+  if (!one_test_ok(kArgs, test, iters) || !signature_out_ok(dev_out, dev_where))
     return (int)hipErrorInvalidValue;
-  Params p{};
-  p.seed = seed;
-  p.tests = test;
-  p.iters = iters;
-  hipLaunchKernelGGL(k_cuscan<false>, dim3(1), dim3(GM_CUSCAN_THREADS), 0, (hipStream_t)stream, p,
-                     (const uint32_t*)nullptr, (DevTable*)nullptr, dev_out, dev_where);
+  hipLaunchKernelGGL(k_cuscan<false>, dim3(1), dim3(GM_CUSCAN_THREADS), 0, (hipStream_t)stream,
+                     params_of(seed, test, iters), (const uint32_t*)nullptr, (DevTable*)nullptr,
+                     dev_out, dev_where);
   return (int)hipGetLastError();
 }
 
 int gm_probe_cuscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed, int min_rounds,
                     int max_rounds, const gm_cuscan_inject_t* inject, gm_cuscan_result_t* out,
                     gm_cuscan_cu_t* cus, int cus_cap, int* n_cus) {
-  if (!out) return (int)hipErrorInvalidValue;
-  memset(out, 0, sizeof(*out));
-  if (n_cus) *n_cus = 0;
-  if (tests_mask == 0 || (tests_mask & ~(uint32_t)GM_CUSCAN_ALL) || !iters_ok(tests_mask, iters) ||
-      !rounds_ok(min_rounds, max_rounds, cus, cus_cap) ||
-      (inject && !inject_ok(inject, tests_mask)))
+  if (!scan_args_ok(kArgs, tests_mask, iters, min_rounds, max_rounds, inject, out, cus, cus_cap,
+                    n_cus))
     return (int)hipErrorInvalidValue;
-  Params p{};
-  p.seed = seed;
-  p.tests = tests_mask;
-  p.iters = iters;
-  if (inject) p.inj = *inject;
   return run_scan(
-      dev, k_cuscan<true>, p, 4 * GM_CUSCAN_SIG_WORDS,
+      dev, k_cuscan<true>, params_of(seed, tests_mask, iters, inject), 4 * GM_CUSCAN_SIG_WORDS,
       [&](uint32_t* exp) {
         for (int i = 0; i < 4; ++i)
           if (tests_mask & (1u << i))

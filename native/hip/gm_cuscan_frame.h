@@ -157,14 +157,52 @@ __device__ __forceinline__ void book_block(uint32_t* lds, const Where& at, uint3
   }
 }
 
-inline bool inject_fields_ok(const gm_cuscan_inject_t* in, uint32_t tests) {
-  return (in->test & tests) && in->thread < GM_CUSCAN_THREADS && in->word < 4 && in->mask != 0 &&
-         (in->id == GM_CUSCAN_ANY || in->id < GM_CUSCAN_IDS);
+// What a scan's entry points check their arguments against: the mask of all its tests (one test
+// is one bit of it) and what it accepts as iters for a mask of tests.
+struct ScanArgs {
+  uint32_t all;
+  bool (*iters_ok)(uint32_t tests, uint32_t iters);
+};
+
+inline bool one_bit_ok(const ScanArgs& s, uint32_t t) {
+  return t != 0 && (t & (t - 1)) == 0 && (t & ~s.all) == 0;
 }
 
-inline bool rounds_ok(int min_rounds, int max_rounds, const gm_cuscan_cu_t* cus, int cus_cap) {
-  return min_rounds >= 1 && max_rounds >= min_rounds && max_rounds <= 1024 && cus_cap >= 0 &&
-         (cus_cap == 0 || cus);
+// _expected and _signature: one test, its iters.
+inline bool one_test_ok(const ScanArgs& s, uint32_t test, uint32_t iters) {
+  return one_bit_ok(s, test) && s.iters_ok(test, iters);
+}
+
+// _signature: a 16-byte aligned table of signatures, a 4-byte aligned {CU id, 4 SIMDs}.
+inline bool signature_out_ok(const uint32_t* dev_out, const uint32_t* dev_where) {
+  return dev_out && !((uintptr_t)dev_out & 15) && dev_where && !((uintptr_t)dev_where & 3);
+}
+
+inline Params params_of(uint64_t seed, uint32_t tests, uint32_t iters,
+                        const gm_cuscan_inject_t* inject = nullptr) {
+  Params p{};
+  p.seed = seed;
+  p.tests = tests;
+  p.iters = iters;
+  if (inject) p.inj = *inject;
+  return p;
+}
+
+// The scan entry point's prologue: the outputs zeroed (false without `out`), then every argument
+// the scans share checked. A false return is hipErrorInvalidValue, before any HIP call.
+inline bool scan_args_ok(const ScanArgs& s, uint32_t tests, uint32_t iters, int min_rounds,
+                         int max_rounds, const gm_cuscan_inject_t* in, gm_cuscan_result_t* out,
+                         const gm_cuscan_cu_t* cus, int cus_cap, int* n_cus) {
+  if (!out) return false;
+  memset(out, 0, sizeof(*out));
+  if (n_cus) *n_cus = 0;
+  if (tests == 0 || (tests & ~s.all) || !s.iters_ok(tests, iters)) return false;
+  if (min_rounds < 1 || max_rounds < min_rounds || max_rounds > 1024 || cus_cap < 0 ||
+      (cus_cap != 0 && !cus))
+    return false;
+  return !in || (one_bit_ok(s, in->test) && (in->test & tests) && in->thread < GM_CUSCAN_THREADS &&
+                 in->word < 4 && in->mask != 0 &&
+                 (in->id == GM_CUSCAN_ANY || in->id < GM_CUSCAN_IDS));
 }
 
 // The scan of device `dev` with the compare form of a scan kernel; the arguments were checked.

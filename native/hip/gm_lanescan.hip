@@ -399,15 +399,9 @@ __global__ __launch_bounds__(GM_CUSCAN_THREADS) void k_lanescan(
   book_block<kCompare>(lds, at, failed, bad, tab, where_out);
 }
 
-bool one_test_bit(uint32_t t) {
-  return t != 0 && (t & (t - 1)) == 0 && (t & ~(uint32_t)GM_LANESCAN_ALL) == 0;
-}
+bool iters_ok(uint32_t, uint32_t iters) { return iters >= 1 && iters <= GM_LANESCAN_MAX_ITERS; }
 
-bool iters_ok(uint32_t iters) { return iters >= 1 && iters <= GM_LANESCAN_MAX_ITERS; }
-
-bool inject_ok(const gm_cuscan_inject_t* in, uint32_t tests) {
-  return one_test_bit(in->test) && inject_fields_ok(in, tests);
-}
+constexpr ScanArgs kArgs = {GM_LANESCAN_ALL, iters_ok};
 
 void fill_table(uint64_t seed, uint32_t* table) {
   for (uint32_t i = 0; i < GM_LANESCAN_TABLE_WORDS; ++i) table[i] = gm_lanescan_salu_table(seed, i);
@@ -418,7 +412,7 @@ void fill_table(uint64_t seed, uint32_t* table) {
 extern "C" {
 
 int gm_probe_lanescan_expected(uint32_t test, uint64_t seed, uint32_t iters, uint32_t* out) {
-  if (!one_test_bit(test) || !iters_ok(iters) || !out) return (int)hipErrorInvalidValue;
+  if (!one_test_ok(kArgs, test, iters) || !out) return (int)hipErrorInvalidValue;
   gm_lanescan_expected_host(test, seed, iters, out);
   return 0;
 }
@@ -441,13 +435,8 @@ int gm_probe_lanescan_lanes(uint32_t* menu, int menu_cap, int* n_menu, uint32_t*
 
 int gm_probe_lanescan_signature(uint32_t test, uint64_t seed, uint32_t iters, uint32_t* dev_out,
                                 uint32_t* dev_where, void* stream) {
-  if (!one_test_bit(test) || !iters_ok(iters) || !dev_out || ((uintptr_t)dev_out & 15) ||
-      !dev_where || ((uintptr_t)dev_where & 3))
+  if (!one_test_ok(kArgs, test, iters) || !signature_out_ok(dev_out, dev_where))
     return (int)hipErrorInvalidValue;
-  Params p{};
-  p.seed = seed;
-  p.tests = test;
-  p.iters = iters;
   // the scalar test's table: copied in on the stream, and the buffer is freed once the block
   // that reads it is done
   DevBuf dtable;
@@ -457,7 +446,8 @@ int gm_probe_lanescan_signature(uint32_t test, uint64_t seed, uint32_t iters, ui
   GM_CHECK(hipMemcpyAsync(dtable.p, table.data(), table.size() * sizeof(uint32_t),
                           hipMemcpyHostToDevice, (hipStream_t)stream));
   hipLaunchKernelGGL(k_lanescan<false>, dim3(1), dim3(GM_CUSCAN_THREADS), 0, (hipStream_t)stream,
-                     p, (const uint32_t*)dtable.p, (DevTable*)nullptr, dev_out, dev_where);
+                     params_of(seed, test, iters), (const uint32_t*)dtable.p, (DevTable*)nullptr,
+                     dev_out, dev_where);
   GM_CHECK(hipGetLastError());
   GM_CHECK(hipStreamSynchronize((hipStream_t)stream));
   return 0;
@@ -466,19 +456,12 @@ int gm_probe_lanescan_signature(uint32_t test, uint64_t seed, uint32_t iters, ui
 int gm_probe_lanescan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed, int min_rounds,
                       int max_rounds, const gm_cuscan_inject_t* inject, gm_cuscan_result_t* out,
                       gm_cuscan_cu_t* cus, int cus_cap, int* n_cus) {
-  if (!out) return (int)hipErrorInvalidValue;
-  memset(out, 0, sizeof(*out));
-  if (n_cus) *n_cus = 0;
-  if (tests_mask == 0 || (tests_mask & ~(uint32_t)GM_LANESCAN_ALL) || !iters_ok(iters) ||
-      !rounds_ok(min_rounds, max_rounds, cus, cus_cap) || (inject && !inject_ok(inject, tests_mask)))
+  if (!scan_args_ok(kArgs, tests_mask, iters, min_rounds, max_rounds, inject, out, cus, cus_cap,
+                    n_cus))
     return (int)hipErrorInvalidValue;
-  Params p{};
-  p.seed = seed;
-  p.tests = tests_mask;
-  p.iters = iters;
-  if (inject) p.inj = *inject;
   return run_scan(
-      dev, k_lanescan<true>, p, (size_t)GM_LANESCAN_EXPECTED_WORDS,
+      dev, k_lanescan<true>, params_of(seed, tests_mask, iters, inject),
+      (size_t)GM_LANESCAN_EXPECTED_WORDS,
       [&](uint32_t* exp) {
         fill_table(seed, exp);
         for (int t = 0; t < GM_LANESCAN_TESTS; ++t)

@@ -173,29 +173,23 @@ __global__ __launch_bounds__(GM_CUSCAN_THREADS) void k_mfmascan(
   book_block<kCompare>(lds, at, failed, bad, tab, where_out);
 }
 
-bool one_format_bit(uint32_t f) {
-  return f != 0 && (f & (f - 1)) == 0 && (f & ~(uint32_t)GM_MFMASCAN_ALL) == 0;
-}
+bool iters_ok(uint32_t, uint32_t iters) { return iters >= 1 && iters <= GM_MFMASCAN_MAX_ITERS; }
 
-bool iters_ok(uint32_t iters) { return iters >= 1 && iters <= GM_MFMASCAN_MAX_ITERS; }
-
-bool inject_ok(const gm_cuscan_inject_t* in, uint32_t formats) {
-  return one_format_bit(in->test) && inject_fields_ok(in, formats);
-}
+constexpr ScanArgs kArgs = {GM_MFMASCAN_ALL, iters_ok};
 
 }  // namespace
 
 extern "C" {
 
 int gm_probe_mfmascan_expected(uint32_t format, uint64_t seed, uint32_t iters, uint32_t* out) {
-  if (!one_format_bit(format) || !iters_ok(iters) || !out) return (int)hipErrorInvalidValue;
+  if (!one_test_ok(kArgs, format, iters) || !out) return (int)hipErrorInvalidValue;
   gm_mfmascan_expected_host(format, seed, iters, out);
   return 0;
 }
 
 int gm_probe_mfmascan_images(uint32_t format, uint64_t seed, uint32_t step, uint32_t* images,
                              uint32_t* scales) {
-  if (!one_format_bit(format) || step >= GM_MFMASCAN_MAX_ITERS || !images || !scales)
+  if (!one_bit_ok(kArgs, format) || step >= GM_MFMASCAN_MAX_ITERS || !images || !scales)
     return (int)hipErrorInvalidValue;
   const int f = __builtin_ctz(format);
   for (uint32_t w = 0; w < 4; ++w)
@@ -211,35 +205,23 @@ int gm_probe_mfmascan_images(uint32_t format, uint64_t seed, uint32_t step, uint
 
 int gm_probe_mfmascan_signature(uint32_t format, uint64_t seed, uint32_t iters, uint32_t* dev_out,
                                 uint32_t* dev_where, void* stream) {
-  if (!one_format_bit(format) || !iters_ok(iters) || !dev_out || ((uintptr_t)dev_out & 15) ||
-      !dev_where || ((uintptr_t)dev_where & 3))
+  if (!one_test_ok(kArgs, format, iters) || !signature_out_ok(dev_out, dev_where))
     return (int)hipErrorInvalidValue;
-  Params p{};
-  p.seed = seed;
-  p.tests = format;
-  p.iters = iters;
   hipLaunchKernelGGL(k_mfmascan<false>, dim3(1), dim3(GM_CUSCAN_THREADS), 0, (hipStream_t)stream,
-                     p, (const uint32_t*)nullptr, (DevTable*)nullptr, dev_out, dev_where);
+                     params_of(seed, format, iters), (const uint32_t*)nullptr, (DevTable*)nullptr,
+                     dev_out, dev_where);
   return (int)hipGetLastError();
 }
 
 int gm_probe_mfmascan(int dev, uint32_t formats_mask, uint32_t iters, uint64_t seed,
                       int min_rounds, int max_rounds, const gm_cuscan_inject_t* inject,
                       gm_cuscan_result_t* out, gm_cuscan_cu_t* cus, int cus_cap, int* n_cus) {
-  if (!out) return (int)hipErrorInvalidValue;
-  memset(out, 0, sizeof(*out));
-  if (n_cus) *n_cus = 0;
-  if (formats_mask == 0 || (formats_mask & ~(uint32_t)GM_MFMASCAN_ALL) || !iters_ok(iters) ||
-      !rounds_ok(min_rounds, max_rounds, cus, cus_cap) ||
-      (inject && !inject_ok(inject, formats_mask)))
+  if (!scan_args_ok(kArgs, formats_mask, iters, min_rounds, max_rounds, inject, out, cus, cus_cap,
+                    n_cus))
     return (int)hipErrorInvalidValue;
-  Params p{};
-  p.seed = seed;
-  p.tests = formats_mask;
-  p.iters = iters;
-  if (inject) p.inj = *inject;
   return run_scan(
-      dev, k_mfmascan<true>, p, (size_t)GM_MFMASCAN_FORMATS * GM_CUSCAN_SIG_WORDS,
+      dev, k_mfmascan<true>, params_of(seed, formats_mask, iters, inject),
+      (size_t)GM_MFMASCAN_FORMATS * GM_CUSCAN_SIG_WORDS,
       [&](uint32_t* exp) {
         for (int f = 0; f < GM_MFMASCAN_FORMATS; ++f)
           if (formats_mask & (1u << f))

@@ -513,7 +513,6 @@ def test_validate_parses_the_cache_scan_options():
         validate.main(["--cache-scan", "--cache-scan-inject", "any:nope:0:0:1"])
     with pytest.raises(SystemExit):
         validate.main(["--cache-scan", "--cache-scan-poke", "icache:0:1"])
-    assert '"cachescan"' in inspect.getsource(validate.main)
 
 
 def test_doctor_passes_the_scan_on_and_names_the_unit_and_test(monkeypatch):
@@ -559,7 +558,6 @@ def test_doctor_passes_the_scan_on_and_names_the_unit_and_test(monkeypatch):
 
 
 def test_the_result_decoder_is_shared_with_the_cu_scan():
-    assert "decode_result" in inspect.getsource(cachescan.scan)
     unit = {"id": 0x225, "xcc": 2, "se": 1, "sh": 0, "cu": 5, "simds_failed": [1, 3],
             "tests_failed": ["l2", "icache"]}
     assert cachescan.describe_failed({"failed": [unit]}) == (

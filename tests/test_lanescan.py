@@ -538,7 +538,6 @@ def test_validate_parses_the_lane_scan_options():
         validate.main(["--lane-scan-inject", "any:xlane:0:0:1"])         # needs --lane-scan
     with pytest.raises(SystemExit):
         validate.main(["--lane-scan", "--lane-scan-inject", "any:nope:0:0:1"])
-    assert '"lanescan"' in inspect.getsource(validate.main)
 
 
 def test_doctor_passes_the_scan_on_and_names_the_unit_and_test(monkeypatch):
@@ -580,7 +579,6 @@ def test_doctor_passes_the_scan_on_and_names_the_unit_and_test(monkeypatch):
 
 
 def test_the_result_decoder_is_shared_with_the_cu_scan():
-    assert "decode_result" in inspect.getsource(lanescan.scan)
     unit = {"id": 0x225, "xcc": 2, "se": 1, "sh": 0, "cu": 5, "simds_failed": [1, 3],
             "tests_failed": ["xlane", "trans"]}
     assert lanescan.describe_failed({"failed": [unit]}) == (

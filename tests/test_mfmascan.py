@@ -347,7 +347,6 @@ def test_validate_parses_the_mfma_scan_options():
         validate.main(["--mfma-scan-inject", "any:mxfp4:0:0:1"])       # needs --mfma-scan
     with pytest.raises(SystemExit):
         validate.main(["--mfma-scan", "--mfma-scan-inject", "any:bf16:0:0:1"])
-    assert "--mfma-scan" in inspect.getsource(validate.main)
 
 
 def test_doctor_passes_the_scan_on_and_names_the_unit_and_format(monkeypatch):
@@ -389,9 +388,9 @@ def test_doctor_passes_the_scan_on_and_names_the_unit_and_format(monkeypatch):
 
 
 def test_the_result_decoder_is_shared_with_the_cu_scan():
-    assert "decode_result" in inspect.getsource(mfmascan.scan)
-    assert "decode_result" in inspect.getsource(cuscan.scan)
     unit = {"id": 0x225, "xcc": 2, "se": 1, "sh": 0, "cu": 5, "simds_failed": [1, 3],
             "formats_failed": ["fp8", "mxfp6"]}
     assert mfmascan.describe_failed({"failed": [unit]}) == (
         "xcc 2 se 1 sh 0 cu 5 (id 0x225) simd 1,3 fp8+mxfp6")
+    assert cuscan.describe_failed({"failed": [unit]}, "formats") == (
+        mfmascan.describe_failed({"failed": [unit]}))
