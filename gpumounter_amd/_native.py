@@ -439,6 +439,17 @@ def probe() -> C.CDLL:
                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.gm_probe_mfmascan_signature.argtypes = lib.gm_probe_cuscan_signature.argtypes
         lib.gm_probe_mfmascan.argtypes = lib.gm_probe_cuscan.argtypes
+        lib.gm_probe_mx_fill.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gm_probe_mxgemm_nt.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p]
+        lib.gm_probe_mxgemm_expected.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32,
+                                                 C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+        lib.gm_probe_mxgemm_kernel_info.argtypes = [C.c_int, C.POINTER(C.c_int),
+                                                    C.POINTER(C.c_int)]
+        lib.gm_probe_mx_burn_in_flip.argtypes = [C.c_int] + lib.gm_probe_burn_in_flip.argtypes
         lib.gm_probe_lanescan_expected.argtypes = lib.gm_probe_cuscan_expected.argtypes
         lib.gm_probe_lanescan_lanes.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int),
                                                 C.POINTER(C.c_uint32)]

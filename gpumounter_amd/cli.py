@@ -6,6 +6,7 @@
     python -m gpumounter_amd topology  [--amdsmi mock] [-n 4]   # xGMI/NUMA placement preview
     python -m gpumounter_amd probe     [--bdf 0000:05:00.0] [--full] [--burn-in 60]  # gfx950 kernels
                                        [--burn-in-flip ELEM:MASK]            # its negative control
+                                       [--burn-in-format bf16,mxfp8,mxfp4]   # also on the MX pipe
                                        [--memtest [SIZE]] [--memtest-passes N]
                                        [--memtest-patterns addr,solid,checker,walk,random]
                                        [--memtest-flip OFFSET:MASK]          # HBM pattern test
@@ -204,6 +205,22 @@ def _burn_in_flip(text):
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _burn_in_formats(text):
+    """argparse type for --burn-in-format: the parser in ops.mxgemm, its refusal a usage error."""
+    from gpumounter_amd.ops import mxgemm
+    try:
+        return mxgemm.parse_burn_in_formats(text)
+    except mxgemm.ProbeError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def _add_burn_in_format(p) -> None:
+    p.add_argument("--burn-in-format", type=_burn_in_formats, default=None, metavar="LIST",
+                   help="with --burn-in: the burn-in's formats, of bf16,mxfp8,mxfp4 (default "
+                        "bf16); each runs for SECONDS, the block-scaled ones as a bit-checked "
+                        "fp8 / fp4 GEMM on the MX matrix pipe")
+
+
 def _atomics_arg(kind):
     """argparse type for the --atomics-* options: the parser in ops.atomics, its refusal a usage
     error."""
@@ -357,6 +374,9 @@ def cmd_probe(args) -> int:
     if args.burn_in_flip and not args.burn_in:
         print("probe: --burn-in-flip needs --burn-in SECONDS", file=sys.stderr)
         return 2                      # a usage error, not a failed burn-in (exit 1)
+    if args.burn_in_format and not args.burn_in:
+        print("probe: --burn-in-format needs --burn-in SECONDS", file=sys.stderr)
+        return 2
     cu, *later = _scans()             # the CU scan: before the host-link and atomics tests
     error = _scan_usage(cu, args, "probe")
     if error:
@@ -425,9 +445,14 @@ def cmd_probe(args) -> int:
     res = [r.to_dict() for r in probe.verify(bdfs, full=args.full)]
     bad = False
     if args.burn_in:
+        from gpumounter_amd.ops import mxgemm
+
         for r in res:
-            r["burn_in"] = probe.burn_in(r["device"], args.burn_in, _flips=args.burn_in_flip)
-            bad |= not r["burn_in"]["ok"]
+            for fmt in args.burn_in_format or ("bf16",):
+                key = mxgemm.burn_in_key(fmt)
+                r[key] = mxgemm.run_burn_in(r["device"], args.burn_in, fmt,
+                                            _flips=args.burn_in_flip)
+                bad |= not r[key]["ok"]
     if args.memtest is not None:
         from gpumounter_amd.ops import memtest
 
@@ -620,6 +645,13 @@ def cmd_doctor(args) -> int:
     if args.atomics_inject and not args.atomics:
         print("doctor: --atomics-inject needs --atomics", file=sys.stderr)
         return 2
+    for option, value, name in (("--burn-in-format", args.burn_in_format, "burn_in_formats"),
+                                ("--burn-in-flip", args.burn_in_flip, "burn_in_flip")):
+        if value and not args.burn_in:
+            print(f"doctor: {option} needs --burn-in SECONDS", file=sys.stderr)
+            return 2
+        if value:
+            extra[name] = value
     if args.atomics:
         extra["atomics"] = True
         if args.atomics_inject:
@@ -680,6 +712,7 @@ def build_parser() -> argparse.ArgumentParser:
                    metavar="ELEM:MASK",
                    help="negative control (repeatable): XOR that bf16 element of the burn-in's "
                         "reference result with MASK; the burn-in must fail")
+    _add_burn_in_format(p)
     _add_memtest_size(p, "HBM pattern test over SIZE bytes (64M, 8G; default: 90 %% of the free "
                          "memory) of every probed GPU (exit 1 on any bad word)")
     p.add_argument("--memtest-passes", type=int, default=1, metavar="N")
@@ -752,6 +785,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also run the gfx950 liveness kernel on every GPU")
     p.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
                    help="with --gpu: sustained bit-checked GEMM load per GPU")
+    p.add_argument("--burn-in-flip", type=_burn_in_flip, action="append", default=None,
+                   metavar="ELEM:MASK",
+                   help="the burn-in's negative control (repeatable), for every chosen format")
+    _add_burn_in_format(p)
     _add_memtest_size(p, "with --gpu: HBM pattern test over SIZE bytes per GPU (default: 90 %% of "
                          "its free memory)")
     _add_doctor_scan(p, cu)

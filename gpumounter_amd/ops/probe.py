@@ -239,14 +239,8 @@ def parse_burn_in_flip(text) -> Tuple[int, int]:
     return elem, mask
 
 
-def burn_in(dev: int, seconds: float = 10.0, n: int = 8192,
-            _flips: Optional[Sequence[Tuple[int, int]]] = None) -> Dict:
-    """Sustained-load check of an attached GPU: back-to-back n³ bf16 GEMMs for ``seconds``,
-    each compared bit-for-bit with the first result (the kernel is deterministic). Any
-    ``mismatches`` means silent data corruption. ``tflops`` is the sustained rate, so
-    throttling shows up as a low number. ``_flips=[(elem, mask), ...]`` is the negative control:
-    those bf16 elements of the reference result are XORed with ``mask`` before the loop, so
-    every iteration must count each 16-byte word they touch."""
+def _burn_in_flips(_flips, n: int):
+    """The burn-ins' flip control, checked: (element indices, the two native arrays)."""
     flips = list(_flips or ())
     elems = [e for e, _ in flips]
     for e, m in flips:
@@ -257,15 +251,31 @@ def burn_in(dev: int, seconds: float = 10.0, n: int = 8192,
         raise ProbeError("burn-in: an element may be flipped only once")
     fe = (C.c_uint64 * max(1, len(flips)))(*elems)
     fm = (C.c_uint16 * max(1, len(flips)))(*[m for _, m in flips])
-    tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
-    _check(_native.probe().gm_probe_burn_in_flip(dev, n, seconds, len(flips), fe, fm,
-                                                 C.byref(tf), C.byref(bad), C.byref(it)),
-           "burn-in")
+    return elems, fe, fm
+
+
+def _burn_in_report(dev: int, n: int, seconds: float, elems, tf, bad, it) -> Dict:
     out = {"device": dev, "n": n, "seconds": seconds, "iterations": it.value,
            "tflops": tf.value, "mismatches": bad.value, "ok": bad.value == 0}
-    if flips:
+    if elems:
         out["flipped_words"] = len({e // 8 for e in elems})
     return out
+
+
+def burn_in(dev: int, seconds: float = 10.0, n: int = 8192,
+            _flips: Optional[Sequence[Tuple[int, int]]] = None) -> Dict:
+    """Sustained-load check of an attached GPU: back-to-back n³ bf16 GEMMs for ``seconds``,
+    each compared bit-for-bit with the first result (the kernel is deterministic). Any
+    ``mismatches`` means silent data corruption. ``tflops`` is the sustained rate, so
+    throttling shows up as a low number. ``_flips=[(elem, mask), ...]`` is the negative control:
+    those bf16 elements of the reference result are XORed with ``mask`` before the loop, so
+    every iteration must count each 16-byte word they touch."""
+    elems, fe, fm = _burn_in_flips(_flips, n)
+    tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
+    _check(_native.probe().gm_probe_burn_in_flip(dev, n, seconds, len(elems), fe, fm,
+                                                 C.byref(tf), C.byref(bad), C.byref(it)),
+           "burn-in")
+    return _burn_in_report(dev, n, seconds, elems, tf, bad, it)
 
 
 def _dev_bytes(t, what: str, align: int = 16, multiple: int = 16) -> int:

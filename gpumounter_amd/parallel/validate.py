@@ -9,7 +9,8 @@ starting a job on them — the reference offers nothing here:
    ``nccl`` (RCCL on ROCm), a checked bf16 all-reduce with ring bus bandwidth
    (:func:`collectives.allreduce_check`);
 4. optionally (``--burn-in SECONDS``) all GPUs under sustained MFMA load at once, each
-   result bit-compared with the first: bf16 GEMMs for SECONDS (:func:`probe.burn_in`). Catches
+   result bit-compared with the first: bf16 GEMMs for SECONDS (:func:`probe.burn_in`), and with
+   ``--burn-in-format`` also block-scaled fp8 / fp4 ones (:func:`mxgemm.burn_in`). Catches
    silent data corruption and throttling that a short probe misses;
 5. optionally (``--memtest [SIZE]``) the HBM pattern test on all GPUs at once
    (:func:`gpumounter_amd.ops.memtest.memtest`): SIZE bytes per GPU, by default 90 % of what is
@@ -111,6 +112,12 @@ def main(argv=None) -> int:
     ap.add_argument("--no-p2p", action="store_true")
     ap.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
                     help="then load every GPU at once with bit-checked GEMMs for SECONDS")
+    ap.add_argument("--burn-in-format", default=None, metavar="LIST",
+                    help="the burn-in's formats, of bf16,mxfp8,mxfp4 (default bf16), one after the "
+                         "other for SECONDS each; needs --burn-in")
+    ap.add_argument("--burn-in-flip", action="append", default=None, metavar="ELEM:MASK",
+                    help="the burn-in's negative control, for every chosen format (see probe "
+                         "--burn-in-flip); needs --burn-in")
     ap.add_argument("--memtest", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the HBM pattern test on every GPU at once over SIZE bytes each "
                          "(64M, 8G; default: 90 %% of the free memory)")
@@ -142,6 +149,18 @@ def main(argv=None) -> int:
             controls[scan.key] = {
                 f"_{name}": text if text is None else getattr(scan.module, f"parse_{name}")(text)
                 for name, text in texts.items()}
+        except ProbeError as e:
+            ap.error(str(e))
+    burn_in_formats, burn_in_flips = ("bf16",), None
+    if args.burn_in_format is not None or args.burn_in_flip is not None:
+        from gpumounter_amd.ops import mxgemm, probe as _probe
+        if not args.burn_in:
+            ap.error("--burn-in-format and --burn-in-flip need --burn-in SECONDS")
+        try:
+            if args.burn_in_format is not None:
+                burn_in_formats = mxgemm.parse_burn_in_formats(args.burn_in_format)
+            if args.burn_in_flip is not None:
+                burn_in_flips = [_probe.parse_burn_in_flip(t) for t in args.burn_in_flip]
         except ProbeError as e:
             ap.error(str(e))
     atomics_inject = None
@@ -198,13 +217,16 @@ def main(argv=None) -> int:
     if args.burn_in and not args.cpu_ranks:
         from concurrent.futures import ThreadPoolExecutor
 
-        from gpumounter_amd.ops import probe
+        from gpumounter_amd.ops import mxgemm
 
         # all GPUs at once (shared power/thermal envelope); ctypes drops the GIL in the call
-        with ThreadPoolExecutor(max_workers=world) as ex:
-            burn = list(ex.map(lambda d: probe.burn_in(d, args.burn_in), range(world)))
-        report["burn_in"] = burn
-        report["ok"] &= all(b["ok"] for b in burn)
+        for fmt in burn_in_formats:
+            with ThreadPoolExecutor(max_workers=world) as ex:
+                burn = list(ex.map(lambda d: mxgemm.run_burn_in(d, args.burn_in, fmt,
+                                                                _flips=burn_in_flips),
+                                   range(world)))
+            report[mxgemm.burn_in_key(fmt)] = burn
+            report["ok"] &= all(b["ok"] for b in burn)
     if args.memtest is not None and not args.cpu_ranks:
         from concurrent.futures import ThreadPoolExecutor
 

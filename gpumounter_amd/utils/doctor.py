@@ -303,10 +303,13 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                atomics_inject=None, mfma_scan: bool = False,
                mfma_scan_inject=None, lane_scan: bool = False,
                lane_scan_inject=None, cache_scan: bool = False,
-               cache_scan_inject=None, cache_scan_poke=None) -> List[Check]:
+               cache_scan_inject=None, cache_scan_poke=None,
+               burn_in_formats=("bf16",)) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
-    sustained bit-checked bf16 GEMM load per GPU. With ``memtest_bytes`` also the HBM pattern
+    sustained bit-checked GEMM load per GPU, once per format in ``burn_in_formats`` (bf16, and the
+    block-scaled mxfp8 and mxfp4 of :func:`gpumounter_amd.ops.mxgemm.burn_in`); a format with a
+    mismatching word fails the check and is named. With ``memtest_bytes`` also the HBM pattern
     test over that many bytes per GPU (negative: 90 % of what is free on it); ``memtest_flip``
     = (offset, mask) is its negative control, ``burn_in_flip`` = [(element, mask), ...] the
     burn-in's (see :func:`probe.burn_in`). With ``cu_scan`` also the per-CU self-test
@@ -333,7 +336,7 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     should not be handed out."""
     given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.hw.inventory import Inventory
-    from gpumounter_amd.ops import cuframe, probe
+    from gpumounter_amd.ops import cuframe, mxgemm, probe
 
     cu, *later = cuframe.registry()   # the CU scan: before the host-link and atomics tests
     try:
@@ -359,11 +362,13 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
             detail = (f"{pr['pci_bus_id']} {arch}: liveness kernel {us:.0f} µs "
                       f"(first launch {cold / 1e3:.0f} ms)")
             status = "ok" if arch == "gfx950" else "warn"
-            if burn_in_s > 0:
-                b = probe.burn_in(d, burn_in_s, _flips=burn_in_flip)
-                detail += (f", burn-in {b['seconds']:g} s {b['tflops']:.0f} TF/s "
-                           f"{b['mismatches']} mismatching words")
-                status = status if b["ok"] else "fail"
+            for fmt in burn_in_formats if burn_in_s > 0 else ():
+                b = mxgemm.run_burn_in(d, burn_in_s, fmt, _flips=burn_in_flip)
+                detail += (f", burn-in {'' if fmt == 'bf16' else fmt + ' '}{b['seconds']:g} s "
+                           f"{b['tflops']:.0f} TF/s {b['mismatches']} mismatching words")
+                if not b["ok"]:
+                    detail += "" if fmt == "bf16" else f", failed: {fmt} burn-in"
+                    status = "fail"
             if memtest_bytes:
                 from gpumounter_amd.ops import memtest
 
@@ -426,7 +431,7 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         host_link_bytes: int = 0, atomics: bool = False, atomics_inject=None,
         mfma_scan: bool = False, mfma_scan_inject=None, lane_scan: bool = False,
         lane_scan_inject=None, cache_scan: bool = False, cache_scan_inject=None,
-        cache_scan_poke=None) -> List[Check]:
+        cache_scan_poke=None, burn_in_formats=None, burn_in_flip=None) -> List[Check]:
     given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.ops import cuframe
 
@@ -434,6 +439,10 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         check_pidns(cfg) + check_systemd(cfg)
     if gpu:
         extra = {}
+        if burn_in_formats is not None:
+            extra["burn_in_formats"] = burn_in_formats
+        if burn_in_flip is not None:
+            extra["burn_in_flip"] = burn_in_flip
         if host_link_bytes:
             extra["host_link_bytes"] = host_link_bytes
         if atomics:

@@ -4,7 +4,7 @@
 // none beat V5, and they were removed: the GEMM is a burn-in load, not a product kernel).
 
 #include "gm_probe.h"
-#include "gm_probe_common.h"
+#include "gm_gemm_shared.h"
 
 namespace {
 
@@ -30,20 +30,9 @@ typedef __attribute__((address_space(1))) void gbl_void;
 }  // namespace g256
 constexpr int kGemmNtDefault = 5;  // profiles/history/r1_gemm: V5 +2.9 % over V1 at 4096³, +0.9 % at 8192³
 
-// XCD-aware block → output tile: bijective for any grid size (the dispatcher deals block ids
-// round-robin over the 8 XCDs, so ids ≡ x mod 8 share XCD x's L2 and get a contiguous range of
-// tiles), then a GROUP_M-deep raster so co-resident tiles share A rows and B columns.
+// The block → tile map (gm_gemm_shared.h) at this kernel's geometry.
 __device__ __forceinline__ void gemm_tile_of(int M, int N, int& tm, int& tn) {
-  using namespace g256;
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int wgid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
-  const int ntm = M / TM, ntn = N / TN;
-  const int per_group = kGroupM * ntn;
-  const int first_m = (wgid / per_group) * kGroupM;
-  const int gsize = min(ntm - first_m, kGroupM);
-  tm = first_m + (wgid % per_group) % gsize;
-  tn = (wgid % per_group) / gsize;
+  gemm_tile_of<g256::TM, g256::TN, g256::kGroupM>(M, N, tm, tn);
 }
 
 // V1 — the plain schedule, kept as the reference point for V5: all 24 fragment reads of the
@@ -252,32 +241,11 @@ __global__ __launch_bounds__(256) void k_fill_bf16(__bf16* dst, size_t n, uint32
   }
 }
 
-// Number of 16-B words that differ between a and b: one ballot + popcount per wave, one
-// atomic per wave.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_count_diff(const u32x4* __restrict__ a,
-                                                    const u32x4* __restrict__ b, size_t n,
-                                                    unsigned long long* count) {
-  unsigned long long local = 0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const u32x4 x = __builtin_nontemporal_load(&a[i]), y = __builtin_nontemporal_load(&b[i]);
-    local += (x.x != y.x) | (x.y != y.y) | (x.z != y.z) | (x.w != y.w);
-  }
-  for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, kWave);
-  if ((threadIdx.x & 63) == 0 && local) atomicAdd(count, local);
-}
-
-// The one launch of each helper kernel: the drivers below and the caller-owned-buffer entry
-// points share them, so a test of the latter runs the grids the former use.
+// The one launch of the fill kernel (the compare kernel's is in gm_gemm_shared.h): the drivers
+// below and the caller-owned-buffer entry points share them, so a test of the latter runs the
+// grids the former use.
 int launch_fill_bf16(void* dst, size_t n, uint32_t seed, hipStream_t s) {
   hipLaunchKernelGGL(k_fill_bf16, dim3(4096), dim3(256), 0, s, (__bf16*)dst, n, seed);
-  return (int)hipGetLastError();
-}
-
-int launch_count_diff(const void* a, const void* b, size_t vec, void* count, hipStream_t s) {
-  hipLaunchKernelGGL(k_count_diff, dim3(2048), dim3(256), 0, s, (const u32x4*)a, (const u32x4*)b,
-                     vec, (unsigned long long*)count);
   return (int)hipGetLastError();
 }
 
@@ -374,65 +342,19 @@ int gm_probe_burn_in_flip(int dev, int n, double seconds, int n_flips,
   *iters = 0;
   if (n <= 0 || n % TM || seconds <= 0) return (int)hipErrorInvalidValue;
   const size_t elems = (size_t)n * n;
-  if (n_flips < 0 || (n_flips > 0 && (!flip_elems || !flip_masks)))
-    return (int)hipErrorInvalidValue;
-  for (int i = 0; i < n_flips; ++i) {
-    if (flip_elems[i] >= elems || flip_masks[i] == 0) return (int)hipErrorInvalidValue;
-    for (int j = 0; j < i; ++j)  // a repeated element could cancel its own flip
-      if (flip_elems[j] == flip_elems[i]) return (int)hipErrorInvalidValue;
-  }
+  if (!burn_in_flips_ok(elems, n_flips, flip_elems, flip_masks)) return (int)hipErrorInvalidValue;
   DeviceGuard g(dev);
   if (!g.ok) return (int)hipErrorInvalidDevice;
-  DevBuf da, db, dref, dc, dcount;
+  DevBuf da, db;
   GM_CHECK(da.alloc(elems * 2));
   GM_CHECK(db.alloc(elems * 2));
-  GM_CHECK(dref.alloc(elems * 2));
-  GM_CHECK(dc.alloc(elems * 2));
-  GM_CHECK(dcount.alloc(sizeof(unsigned long long)));
-  GM_CHECK(hipMemset(dcount.p, 0, sizeof(unsigned long long)));
   int e = launch_fill_bf16(da.p, elems, 0x5151u, nullptr);
   if (!e) e = launch_fill_bf16(db.p, elems, 0xa3a3u, nullptr);
-  if (!e) e = gm_probe_gemm_nt(da.p, db.p, dref.p, n, n, n, nullptr);  // the reference result
   if (e) return e;
-  // Negative control: corrupt the finished reference, through the host like the memtest's flip.
-  // The blocking copies on the null stream wait for the GEMM; the loop below is untouched.
-  for (int i = 0; i < n_flips; ++i) {
-    uint16_t* at = (uint16_t*)dref.p + flip_elems[i];
-    uint16_t v = 0;
-    GM_CHECK(hipMemcpy(&v, at, sizeof(v), hipMemcpyDeviceToHost));
-    v ^= flip_masks[i];
-    GM_CHECK(hipMemcpy(at, &v, sizeof(v), hipMemcpyHostToDevice));
-  }
-  Events ev;
-  GM_CHECK(ev.create());
-  GM_CHECK(hipEventRecord(ev.e0, nullptr));
-  const double t0 = now_s();
-  const size_t vec = elems / 8;  // 16-B compares
-  int done = 0;
-  // Batches of 8 GEMMs, each result compared bit-for-bit with the first one: the kernel is
-  // deterministic (fixed reduction order, no atomics), so any difference is a hardware fault.
-  while (!e) {
-    for (int i = 0; i < 8 && !e; ++i) {
-      e = gm_probe_gemm_nt(da.p, db.p, dc.p, n, n, n, nullptr);
-      if (!e) e = launch_count_diff(dc.p, dref.p, vec, dcount.p, nullptr);
-      ++done;
-    }
-    if (!e) e = (int)hipDeviceSynchronize();
-    const double el = now_s() - t0;
-    if (el >= seconds) break;
-  }
-  if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
-  if (!e) e = (int)hipEventSynchronize(ev.e1);
-  float ms = 0;
-  if (!e) e = elapsed_ms(ev.e0, ev.e1, &ms);
-  unsigned long long bad = 0;
-  if (!e) e = (int)hipMemcpy(&bad, dcount.p, sizeof(bad), hipMemcpyDeviceToHost);
-  if (e) return e;
-  *iters = done;
-  *mismatches = bad;
-  // compare kernels are included in the wall time; they move 2 × n² × 2 B per GEMM (< 1 %)
-  if (ms > 0) *tflops = 2.0 * n * (double)n * n * done / (ms * 1e-3) / 1e12;
-  return 0;
+  return burn_in_loop(
+      n, seconds, n_flips, flip_elems, flip_masks,
+      [&](void* c) { return gm_probe_gemm_nt(da.p, db.p, c, n, n, n, nullptr); }, tflops,
+      mismatches, iters);
 }
 
 }  // extern "C"

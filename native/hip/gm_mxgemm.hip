@@ -1,0 +1,260 @@
+// gm_mxgemm.hip — the block-scaled (MX) burn-in GEMM for gfx950: C[M,N] (bf16) = A[M,K] · Bt[N,K]ᵀ
+// with fp8 (e4m3) or fp4 (e2m1) operands and one E8M0 scale per 32 elements of K, on
+// v_mfma_scale_f32_16x16x128_f8f6f4; its operand fills, its host expected values and its burn-in
+// (the loop of gm_gemm_shared.h, shared with the bf16 GEMM). Part of libgm_probe.so.
+// Value model: gm_mxgemm_ref.h, formulas in gm_probe.h. Measurements: profiles/mxgemm/.
+
+#include "gm_probe.h"
+#include "gm_gemm_shared.h"
+#include "gm_mxgemm_ref.h"
+
+namespace {
+
+// ------------------------------------------------------------------ MX GEMM, 256² tile
+// The geometry of the bf16 kernel (gm_gemm.hip, k_gemm_nt256): 256×256 output tile, 512 threads
+// = 8 waves as 2(M)×4(N), each wave 128×64 as 8×4 16x16 accumulators; operands HBM→LDS with
+// global_load_lds_dwordx4, two stages, the same XOR swizzle of the 16-B chunk index with
+// (row>>1)&7; the same block → tile map. A K-tile is 128 bytes of every row, as there, so the
+// byte layout carries over: 128 elements of fp8 (one MFMA per accumulator), 256 of fp4 (two).
+//
+// Lane maps of v_mfma_scale_f32_16x16x128_f8f6f4 (lane l holds row / column l & 15, g = l >> 4):
+//   fp8: bytes 0-15 are k = 16 g + j, bytes 16-31 are k = 64 + 16 g + (j - 16): logical chunks g
+//        and 4 + g of the row's 128 bytes, the two reads of the bf16 kernel's two k-steps;
+//   fp4: the 16 bytes are k = 32 g + 2 j, 2 j + 1 (low nibble first): chunk g of the 64 bytes of
+//        one 128-element step, again the bf16 kernel's read, once per step;
+//   the scale of row r, block s (k in [32 s, 32 s + 32)) is read from lane r + 16 s, byte 0.
+// (profiles/r3_mx/README.md for fp8; profiles/mxgemm/lanemap.json for fp4.)
+//
+// Scales: one dword (fp8) or two (fp4) per row and K-tile, staged by one global_load_lds_dword
+// per thread and step (thread t: operand t >> 8, row t & 255) into 4 KiB per stage behind the
+// operand stages; a lane reads its byte with ds_read_u8 right before the MFMA that uses it.
+namespace mx256 {
+constexpr int TM = 256, TN = 256, kRowBytes = 128, kThreads = 512, kGroupM = 8;
+constexpr int kTileBytes = TM * kRowBytes;     // 32 KiB: one operand, one stage
+constexpr int kStageBytes = 2 * kTileBytes;    // A + Bt
+constexpr int kScaleStep = (TM + TN) * 4;      // 2 KiB: every row's 4 scale bytes of one step
+constexpr int kScaleStage = 2 * kScaleStep;    // fp4 has two steps per K-tile
+constexpr int kScaleBase = 2 * kStageBytes;    // 128 KiB of operands first
+constexpr int kLdsBytes = kScaleBase + 2 * kScaleStage;  // 136 KiB of the 160 KiB LDS
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(1))) void gbl_void;
+}  // namespace mx256
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+// The operand registers of one MFMA from the LDS stage `sb`: fp8 the two chunks of the lane's
+// row, fp4 the one chunk of step kk (the upper four registers are not read by the instruction).
+template <int FMT>
+__device__ __forceinline__ i32x8 mx_fragment(const char* sb, int off, int kk) {
+  if constexpr (FMT == GM_MX_FP8) {
+    const i32x4 lo = *reinterpret_cast<const i32x4*>(sb + off);
+    const i32x4 hi = *reinterpret_cast<const i32x4*>(sb + (off ^ 64));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  } else {
+    const i32x4 v = *reinterpret_cast<const i32x4*>(sb + (off ^ (kk << 6)));
+    return __builtin_shufflevector(v, v, 0, 1, 2, 3, -1, -1, -1, -1);
+  }
+}
+
+template <int FMT>
+__global__ __launch_bounds__(512) void k_mxgemm_nt(const uint8_t* __restrict__ A,
+                                                   const uint8_t* __restrict__ sA,
+                                                   const uint8_t* __restrict__ Bt,
+                                                   const uint8_t* __restrict__ sB,
+                                                   __bf16* __restrict__ C, int M, int N, int K) {
+  using namespace mx256;
+  constexpr int kSteps = FMT == GM_MX_FP4 ? 2 : 1;  // MFMAs of K = 128 per accumulator and K-tile
+  __shared__ __attribute__((aligned(1024))) char lds[kLdsBytes];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  int tm, tn;
+  gemm_tile_of<TM, TN, kGroupM>(M, N, tm, tn);
+
+  // Operand staging, as in k_gemm_nt256: wave w moves 1 KiB chunks c = w + 8i of each operand's
+  // 256-row tile; lane l writes row 8c + (l>>3), slot l&7 = logical chunk (l&7) ^ ((row>>1)&7).
+  const size_t row_bytes = gm_mx_row_bytes(FMT, (size_t)K), srow_bytes = (size_t)K / GM_MX_BLOCK;
+  const int srow = 8 * wave + (lane >> 3);
+  const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
+  const uint8_t* a_src = A + (size_t)(tm * TM + srow) * row_bytes + schunk * 16;
+  const uint8_t* b_src = Bt + (size_t)(tn * TN + srow) * row_bytes + schunk * 16;
+  const size_t row64 = 64 * row_bytes;
+  // Scale staging: waves 0-3 move A's rows 64 w + l, waves 4-7 Bt's, 4 bytes per step.
+  const uint8_t* s_src = wave < 4 ? sA + (size_t)(tm * TM + tid) * srow_bytes
+                                  : sB + (size_t)(tn * TN + tid - TM) * srow_bytes;
+
+  auto stage = [&](int buf, int t) {
+    char* base = lds + buf * kStageBytes + wave * 1024;
+    const size_t k0 = (size_t)t * kRowBytes;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      __builtin_amdgcn_global_load_lds((gbl_void*)(a_src + i * row64 + k0),
+                                       (lds_void*)(base + i * 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_void*)(b_src + i * row64 + k0),
+                                       (lds_void*)(base + kTileBytes + i * 8192), 16, 0, 0);
+    }
+    char* sbase = lds + kScaleBase + buf * kScaleStage + wave * 256;
+#pragma unroll
+    for (int kk = 0; kk < kSteps; ++kk)
+      __builtin_amdgcn_global_load_lds((gbl_void*)(s_src + ((size_t)t * kSteps + kk) * 4),
+                                       (lds_void*)(sbase + kk * kScaleStep), 4, 0, 0);
+  };
+
+  // Fragment reads: lane l reads row (l&15) of a 16-row block at logical chunk l>>4 (4 + l>>4).
+  const int frow = lane & 15, fgrp = lane >> 4;
+  const int foff0 = frow * 128 + ((fgrp ^ (frow >> 1)) << 4);
+  const int a_off = wm * 128 * 128 + foff0;
+  const int b_off = kTileBytes + wn * 64 * 128 + foff0;
+  // Scale reads: byte l>>4 (the block whose scale this lane supplies) of the row's dword.
+  const int sa_off = (wm * 128 + frow) * 4 + fgrp;
+  const int sb_off = (TM + wn * 64 + frow) * 4 + fgrp;
+
+  f32x4 acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nt = K / gm_mx_tile_k(FMT);
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int t = 0; t < nt; ++t) {
+    const int cur = t & 1;
+    if (t + 1 < nt) stage(cur ^ 1, t + 1);
+    const char* sb = lds + cur * kStageBytes;
+    const uint8_t* ss = reinterpret_cast<const uint8_t*>(lds) + kScaleBase + cur * kScaleStage;
+#pragma unroll
+    for (int kk = 0; kk < kSteps; ++kk) {
+      i32x8 bfr[4];
+      int bsc[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        bfr[j] = mx_fragment<FMT>(sb, b_off + j * 2048, kk);
+        bsc[j] = ss[kk * kScaleStep + sb_off + j * 64];
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const i32x8 af = mx_fragment<FMT>(sb, a_off + i * 2048, kk);
+        const int asc = ss[kk * kScaleStep + sa_off + i * 64];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bfr[j], acc[i][j], FMT,
+                                                                       FMT, 0, asc, 0, bsc[j]);
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // Epilogue: C/D map of the 16x16 shapes: col = l&15, row = 4(l>>4) + reg.
+  const int crow = tm * TM + wm * 128 + 4 * (lane >> 4);
+  const int ccol = tn * TN + wn * 64 + (lane & 15);
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] = (__bf16)acc[i][j][r];
+}
+
+// The packed element bytes of an operand, then its scale bytes: one grid-stride loop each.
+__global__ __launch_bounds__(256) void k_mx_fill(int fmt, int cls, uint32_t seed, uint8_t* elems,
+                                                 size_t elem_bytes, uint8_t* scales,
+                                                 size_t scale_bytes, uint32_t kblocks) {
+  const size_t first = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = first; i < elem_bytes; i += stride)
+    elems[i] = (uint8_t)gm_mx_packed_byte(fmt, cls, seed, i);
+  for (size_t i = first; i < scale_bytes; i += stride)
+    scales[i] = (uint8_t)gm_mx_scale(cls, seed, (uint32_t)(i / kblocks), (uint32_t)(i % kblocks),
+                                     kblocks);
+}
+
+bool shape_ok(int fmt, int M, int N, int K) {
+  return gm_mx_format_ok(fmt) && M > 0 && N > 0 && K > 0 && M % mx256::TM == 0 &&
+         N % mx256::TN == 0 && K % gm_mx_tile_k(fmt) == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gm_probe_mx_fill(int fmt, int cls, uint32_t seed, int rows, int K, void* elems, void* scales,
+                     void* stream) {
+  if (!gm_mx_format_ok(fmt) || !gm_mx_class_ok(cls) || rows <= 0 || K <= 0 || K % GM_MX_BLOCK ||
+      !elems || !scales)
+    return (int)hipErrorInvalidValue;
+  const size_t eb = (size_t)rows * gm_mx_row_bytes(fmt, (size_t)K);
+  const uint32_t kblocks = (uint32_t)K / GM_MX_BLOCK;
+  hipLaunchKernelGGL(k_mx_fill, dim3(4096), dim3(256), 0, (hipStream_t)stream, fmt, cls, seed,
+                     (uint8_t*)elems, eb, (uint8_t*)scales, (size_t)rows * kblocks, kblocks);
+  return (int)hipGetLastError();
+}
+
+int gm_probe_mxgemm_nt(int fmt, const void* A, const void* sA, const void* Bt, const void* sB,
+                       void* C, int M, int N, int K, void* stream) {
+  using namespace mx256;
+  if (!shape_ok(fmt, M, N, K) || !A || !sA || !Bt || !sB || !C || ((uintptr_t)A & 15) ||
+      ((uintptr_t)Bt & 15) || ((uintptr_t)sA & 3) || ((uintptr_t)sB & 3) || ((uintptr_t)C & 1))
+    return (int)hipErrorInvalidValue;
+  const dim3 grid((M / TM) * (N / TN)), block(kThreads);
+  if (fmt == GM_MX_FP4)
+    hipLaunchKernelGGL(k_mxgemm_nt<GM_MX_FP4>, grid, block, 0, (hipStream_t)stream,
+                       (const uint8_t*)A, (const uint8_t*)sA, (const uint8_t*)Bt,
+                       (const uint8_t*)sB, (__bf16*)C, M, N, K);
+  else
+    hipLaunchKernelGGL(k_mxgemm_nt<GM_MX_FP8>, grid, block, 0, (hipStream_t)stream,
+                       (const uint8_t*)A, (const uint8_t*)sA, (const uint8_t*)Bt,
+                       (const uint8_t*)sB, (__bf16*)C, M, N, K);
+  return (int)hipGetLastError();
+}
+
+int gm_probe_mxgemm_expected(int fmt, int cls, uint32_t seed_a, uint32_t seed_b, int M, int N,
+                             int K, uint16_t* c, double* ref, double* abs_sum) {
+  if (!gm_mx_format_ok(fmt) || !gm_mx_class_ok(cls) || M <= 0 || N <= 0 || K <= 0 ||
+      K % GM_MX_BLOCK || (cls == GM_MX_RANDOM ? !ref || !abs_sum : !c))
+    return (int)hipErrorInvalidValue;
+  gm_mxgemm_expected_host(fmt, cls, seed_a, seed_b, M, N, K, c, ref, abs_sum);
+  return 0;
+}
+
+int gm_probe_mxgemm_kernel_info(int fmt, int* num_regs, int* scratch_bytes) {
+  if (!gm_mx_format_ok(fmt) || !num_regs || !scratch_bytes) return (int)hipErrorInvalidValue;
+  hipFuncAttributes attr;
+  GM_CHECK(hipFuncGetAttributes(&attr, fmt == GM_MX_FP4 ? (const void*)k_mxgemm_nt<GM_MX_FP4>
+                                                        : (const void*)k_mxgemm_nt<GM_MX_FP8>));
+  *num_regs = attr.numRegs;
+  *scratch_bytes = (int)attr.localSizeBytes;
+  return 0;
+}
+
+int gm_probe_mx_burn_in_flip(int dev, int fmt, int n, double seconds, int n_flips,
+                             const uint64_t* flip_elems, const uint16_t* flip_masks,
+                             double* tflops, uint64_t* mismatches, int* iters) {
+  *tflops = 0;
+  *mismatches = 0;
+  *iters = 0;
+  if (!shape_ok(fmt, n, n, n) || seconds <= 0) return (int)hipErrorInvalidValue;
+  if (!burn_in_flips_ok((size_t)n * n, n_flips, flip_elems, flip_masks))
+    return (int)hipErrorInvalidValue;
+  DeviceGuard g(dev);
+  if (!g.ok) return (int)hipErrorInvalidDevice;
+  const size_t eb = (size_t)n * gm_mx_row_bytes(fmt, (size_t)n), sb = (size_t)n * n / GM_MX_BLOCK;
+  DevBuf da, db, dsa, dsb;
+  GM_CHECK(da.alloc(eb));
+  GM_CHECK(db.alloc(eb));
+  GM_CHECK(dsa.alloc(sb));
+  GM_CHECK(dsb.alloc(sb));
+  int e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0x5151u, n, n, da.p, dsa.p, nullptr);
+  if (!e) e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0xa3a3u, n, n, db.p, dsb.p, nullptr);
+  if (e) return e;
+  return burn_in_loop(
+      n, seconds, n_flips, flip_elems, flip_masks,
+      [&](void* c) { return gm_probe_mxgemm_nt(fmt, da.p, dsa.p, db.p, dsb.p, c, n, n, n, nullptr); },
+      tflops, mismatches, iters);
+}
+
+}  // extern "C"

@@ -417,6 +417,70 @@ int gm_probe_mfmascan(int dev, uint32_t formats_mask, uint32_t iters, uint64_t s
                       int min_rounds, int max_rounds, const gm_cuscan_inject_t* inject,
                       gm_cuscan_result_t* out, gm_cuscan_cu_t* cus, int cus_cap, int* n_cus);
 
+// ------------------------------------------------------------------ MX GEMM burn-in
+// The burn-in's second load: a GEMM on the block-scaled matrix pipe
+// (v_mfma_scale_f32_16x16x128_f8f6f4), HBM → LDS → MFMA → HBM like the bf16 one, every result
+// compared bit for bit with the first. The code is gm_mxgemm_ref.h (shared by the host and the
+// fill kernel) and native/hip/gm_mxgemm.hip.
+//
+// Formats (`fmt` is the instruction's format field): 0 = mxfp8, OCP e4m3 (bias 7, subnormals, no
+// infinities, 0x7f / 0xff NaN); 4 = mxfp4, e2m1 (nibble n: magnitude (0, 1/2, 1, 3/2, 2, 3, 4, 6)
+// [n & 7], negative when n & 8).
+//
+// Operands. A[M][K] and Bt[N][K] are K-major and packed: fp8 one byte per element; fp4 two
+// elements per byte, element 2 i in the low nibble of byte i. Scales sA[M][K/32], sB[N][K/32]:
+// one E8M0 byte per row and 32 elements of K, row-major, 127 = 1.0. C[M][N] is bf16:
+//   C[i][j] = bf16( sum over k of a(i,k) * 2^(sA[i][k/32] - 127) * b(j,k) * 2^(sB[j][k/32] - 127) )
+// summed in fp32 by the matrix core, rounded to nearest even at the end.
+//
+// Fill. With h(i, s) = the hash of gm_probe_fill_bf16 ((u32)i * 2654435761 ^ s; h ^= h >> 15;
+// h *= 2246822519; h ^= h >> 13), element e = row * K + k of an operand with seed `seed` has
+// H = h(e, seed) and the code
+//   class 0 exact    nibble n = H >> 28; fp4: n itself; fp8: the e4m3 code of n's e2m1 value
+//                    (the matrix-core scan's table: magnitudes 00 30 38 3c 40 44 48 4c, sign 0x80)
+//   class 1 blocks   nibble (0, 2, 4, 10, 12)[(H >> 8) % 5], i.e. 0, 1, 2, -1, -2; coded as above
+//   class 2 random   fp4: nibble H >> 28. fp8: byte b = H >> 24, and where (b & 0x7f) == 0x7f
+//                    (a NaN code) b = (b & 0x80) | ((H >> 8) & 0x7e) instead
+// and the scale byte of (row, K-block kb), with S = seed ^ 0x5ca1e5ca and kblocks = K / 32:
+//   exact    125 + (h(row, S) >> 30)                    125..128, the same along K
+//   blocks   127 + (h(row * kblocks + kb, S) >> 31)     127 or 128, different along K
+//   random   123 + (h(row * kblocks + kb, S) >> 29)     123..130
+// Indices are hashed as 32 bits. A and Bt are filled with different seeds.
+//
+// What each class checks. exact: every product is a multiple of 2^-2 * 2^(sA + sB - 254) and at
+// most 144 of them, all products of one output share one scale, so the sum is exact in fp32 in
+// any order while 144 * K < 2^24 (in units of 2^-6, the smallest scale: 9216 * K < 2^24). blocks:
+// scaled operands are 0, ±1, ±2, ±4, products integers of at most 16 in magnitude, a 128-term sum
+// at most 2048: exact in any order, and a scale applied to the wrong k changes the result, which
+// `exact` cannot see. random: the load; no NaN code, |scaled value| <= 448 * 8, so no infinity at
+// any K an int can hold. The result rounds, so it is checked against the float64 sum `ref` with
+// the bound |C - ref| <= 2^-9 * sum|product| + 2^-8 * |ref|.
+//
+// Fills `rows` rows of K elements (K % 32 == 0) and their rows * K/32 scale bytes, on the current
+// device, asynchronous on `stream`. Bad arguments: hipErrorInvalidValue before any HIP call.
+int gm_probe_mx_fill(int fmt, int cls, uint32_t seed, int rows, int K, void* elems, void* scales,
+                     void* stream);
+// The GEMM on device pointers: 256×256 tiles, a K-tile of 128 bytes per row. M % 256 == 0,
+// N % 256 == 0, K % 128 == 0 (fp8) or K % 256 == 0 (fp4), A and Bt 16-byte, sA and sB 4-byte,
+// C 2-byte aligned: checked before any HIP call. Asynchronous on `stream` (may be NULL).
+int gm_probe_mxgemm_nt(int fmt, const void* A, const void* sA, const void* Bt, const void* sB,
+                       void* C, int M, int N, int K, void* stream);
+// Host only, no GPU: the expected result for operands filled with (fmt, cls, seed_a) and
+// (fmt, cls, seed_b), any M, N > 0 and K % 32 == 0. exact, blocks: c[i * N + j] = the bf16 bits of
+// the exact integer sum (ref, abs_sum unused, may be NULL). random: ref[i * N + j] = the float64
+// sum in k order and abs_sum[i * N + j] = the sum of |product| (c unused, may be NULL).
+int gm_probe_mxgemm_expected(int fmt, int cls, uint32_t seed_a, uint32_t seed_b, int M, int N,
+                             int K, uint16_t* c, double* ref, double* abs_sum);
+// Registers and scratch bytes of the format's kernel (the accumulators must stay in registers).
+int gm_probe_mxgemm_kernel_info(int fmt, int* num_regs, int* scratch_bytes);
+// The MX burn-in: gm_probe_burn_in_flip's contract and loop with gm_probe_mxgemm_nt on
+// random-class n × n operands (seeds 0x5151, 0xa3a3) as the GEMM. n % 256 == 0; the flips are
+// bf16 elements of the n × n reference; *mismatches == *iters × (distinct 16-byte words among the
+// flipped elements); *tflops counts 2 n³ per GEMM, compare kernels included.
+int gm_probe_mx_burn_in_flip(int dev, int fmt, int n, double seconds, int n_flips,
+                             const uint64_t* flip_elems, const uint16_t* flip_masks,
+                             double* tflops, uint64_t* mismatches, int* iters);
+
 // ------------------------------------------------------------------ lane scan
 // The CU scan's frame again (one 256-thread block per CU, so one wave per SIMD; the whole LDS
 // declared; the CU id read from the registers; a host-computed table compared bit for bit) around
