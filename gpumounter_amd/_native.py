@@ -276,6 +276,10 @@ class CachescanTiming(C.Structure):   # gm_cachescan_timing_t: [test][min, media
                 ("blocks", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class LdsscanPoke(C.Structure):       # gm_ldsscan_poke_t
+    _fields_ = [("test", C.c_uint32), ("word_offset", C.c_uint32), ("mask", C.c_uint32)]
+
+
 HOSTLINK_LEGS = 6             # native/include/gm_probe.h GM_HOSTLINK_LEGS
 HOSTLINK_MAX_RECORDS = 16     # GM_HOSTLINK_MAX_RECORDS
 HOSTLINK_MAX_BLOCKS = 1024    # GM_HOSTLINK_MAX_BLOCKS
@@ -469,6 +473,17 @@ def probe() -> C.CDLL:
                                            C.POINTER(CachescanTiming)]
         lib.gm_probe_cachescan_kernel_info.argtypes = [C.POINTER(C.c_int)] * 3
         lib.gm_probe_cachescan_geometry.argtypes = [C.POINTER(C.c_uint32)] * 4
+        lib.gm_probe_ldsscan_expected.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32,
+                                                  C.POINTER(LdsscanPoke), C.POINTER(C.c_uint32)]
+        lib.gm_probe_ldsscan_signature.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32,
+                                                   C.POINTER(LdsscanPoke), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
+        lib.gm_probe_ldsscan.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int,
+                                         C.c_int, C.POINTER(CuscanInject), C.POINTER(LdsscanPoke),
+                                         C.POINTER(CuscanResult), C.POINTER(CuscanCu), C.c_int,
+                                         C.POINTER(C.c_int)]
+        lib.gm_probe_ldsscan_kernel_info.argtypes = [C.POINTER(C.c_int)] * 2
+        lib.gm_probe_ldsscan_geometry.argtypes = [C.POINTER(C.c_uint32)] * 4
         lib.gm_probe_hostlink_geometry.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.gm_probe_hostlink_unroll.argtypes = [C.c_int]
         lib.gm_probe_hostlink_kwrite.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,

@@ -245,7 +245,7 @@ def _add_atomics(p, what: str) -> None:
 def _scans():
     from gpumounter_amd.ops import cuframe
 
-    return cuframe.registry()
+    return cuframe.scans()
 
 
 def _scan_arg(scan, kind):

@@ -29,7 +29,8 @@ a load was served; they are reported and never judged.
 
 What it cannot tell: the Infinity Cache cannot be targeted; residency is observed, not
 guaranteed; the L1 and instruction-cache sizes are assumptions; a corrupted instruction may fault
-rather than miscompute; LDS atomics, clocks and thermals are not covered. No silent fallback: a
+rather than miscompute; clocks and thermals are not covered (LDS atomics are in
+:mod:`gpumounter_amd.ops.ldsscan`). No silent fallback: a
 missing ``libgm_probe.so`` or a HIP failure raises.
 """
 from __future__ import annotations

@@ -4,12 +4,12 @@ registers, 4 signature words per thread and test compared bit for bit with a tab
 host, and one result shape.
 
 A scan is a :class:`Scan` descriptor in its own module (``SCAN`` in :mod:`.cuscan`,
-:mod:`.mfmascan`, :mod:`.lanescan`, :mod:`.cachescan`), next to its tables and the functions only
+:mod:`.mfmascan`, :mod:`.lanescan`, :mod:`.cachescan`, :mod:`.ldsscan`), next to its tables and the functions only
 it has. The descriptor's methods are everything the scans do alike: the name and bit lookups, the
 parsers, the argument checks, ``expected``, ``signature`` and ``scan``. The command line, ``doctor``
-and ``validate`` walk :func:`registry` and know no scan by name. Adding a scan: its kernel and
-host reference, a module with a ``SCAN`` and the public functions, its name in :data:`MODULES`,
-the three entry points in ``_native.py`` and its keyword parameters in ``doctor``.
+and ``validate`` walk :func:`scans` and know no scan by name. Adding a scan: its kernel and
+host reference, a module with a ``SCAN`` and the public functions, its name in
+:data:`MORE_MODULES`, the three entry points in ``_native.py`` and its keyword parameters in ``doctor``.
 
 Every refusal is made here, in Python, before the native library is reached.
 """
@@ -28,12 +28,20 @@ MAX_ROUNDS = 1024
 DEFAULT_SEED = 0x243F6A8885A308D3
 ANY = "any"
 MODULES = ("cuscan", "mfmascan", "lanescan", "cachescan")    # the order of every report
+MORE_MODULES = ("ldsscan",)     # the scans added since: they run and report after MODULES'
 
 
 def registry() -> Tuple["Scan", ...]:
     """The scans' descriptors in the order of :data:`MODULES`. The CU scan is the first: it runs
     before the host-link and atomics tests, the later scans after them."""
     return tuple(importlib.import_module(f"{__package__}.{m}").SCAN for m in MODULES)
+
+
+def scans() -> Tuple["Scan", ...]:
+    """Every scan's descriptor: :func:`registry`'s four, then those of :data:`MORE_MODULES`. This
+    is what the command line, ``doctor`` and ``validate`` walk."""
+    return registry() + tuple(importlib.import_module(f"{__package__}.{m}").SCAN
+                              for m in MORE_MODULES)
 
 
 def decode_id(cu_id: int) -> Dict[str, int]:

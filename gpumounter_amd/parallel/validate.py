@@ -34,7 +34,11 @@ starting a job on them — the reference offers nothing here:
 11. optionally (``--cache-scan``) the per-CU cache scan on all GPUs at once
    (:func:`gpumounter_amd.ops.cachescan.scan`): a march served by the L2, hit and replacement
    passes through the vector L1, a pointer chase through the scalar data cache and a body larger
-   than the instruction cache on every compute unit.
+   than the instruction cache on every compute unit;
+12. optionally (``--lds-scan``) the per-CU LDS scan on all GPUs at once
+   (:func:`gpumounter_amd.ops.ldsscan.scan`): sub-dword, wide and paired LDS accesses, the LDS
+   atomics, the bank crossbar at every conflict degree, the transposing read and direct
+   global-to-LDS loads on every compute unit.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -121,7 +125,7 @@ def main(argv=None) -> int:
     ap.add_argument("--memtest", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the HBM pattern test on every GPU at once over SIZE bytes each "
                          "(64M, 8G; default: 90 %% of the free memory)")
-    cu, *later = cuframe.registry()   # the CU scan: before the host-link and atomics tests
+    cu, *later = cuframe.scans()      # the CU scan: before the host-link and atomics tests
     ap.add_argument("--cu-scan", action="store_true",
                     help=f"then the {cu.title} on every GPU at once")
     ap.add_argument("--host-link", nargs="?", const="auto", default=None, metavar="SIZE",

@@ -304,7 +304,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                mfma_scan_inject=None, lane_scan: bool = False,
                lane_scan_inject=None, cache_scan: bool = False,
                cache_scan_inject=None, cache_scan_poke=None,
-               burn_in_formats=("bf16",)) -> List[Check]:
+               burn_in_formats=("bf16",), lds_scan: bool = False,
+               lds_scan_inject=None, lds_scan_poke=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked GEMM load per GPU, once per format in ``burn_in_formats`` (bf16, and the
@@ -332,13 +333,16 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     reach every CU is stated, not failed; ``lane_scan_inject`` is its negative control. With
     ``cache_scan`` also the per-CU cache scan (:func:`gpumounter_amd.ops.cachescan.scan`: vector
     L1, L2, scalar and instruction caches), failed, named and stated in the same way;
-    ``cache_scan_inject`` and ``cache_scan_poke`` are its negative controls. A GPU that fails here
-    should not be handed out."""
+    ``cache_scan_inject`` and ``cache_scan_poke`` are its negative controls. With ``lds_scan``
+    also the per-CU LDS scan (:func:`gpumounter_amd.ops.ldsscan.scan`: access widths, LDS atomics,
+    bank crossbar, transposing read, global-to-LDS loads), failed, named and stated in the same
+    way; ``lds_scan_inject`` and ``lds_scan_poke`` are its negative controls. A GPU that fails
+    here should not be handed out."""
     given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import cuframe, mxgemm, probe
 
-    cu, *later = cuframe.registry()   # the CU scan: before the host-link and atomics tests
+    cu, *later = cuframe.scans()      # the CU scan: before the host-link and atomics tests
     try:
         n = probe.device_count()
     except Exception as e:  # noqa: BLE001 - no HIP runtime / driver
@@ -431,7 +435,8 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         host_link_bytes: int = 0, atomics: bool = False, atomics_inject=None,
         mfma_scan: bool = False, mfma_scan_inject=None, lane_scan: bool = False,
         lane_scan_inject=None, cache_scan: bool = False, cache_scan_inject=None,
-        cache_scan_poke=None, burn_in_formats=None, burn_in_flip=None) -> List[Check]:
+        cache_scan_poke=None, burn_in_formats=None, burn_in_flip=None,
+        lds_scan: bool = False, lds_scan_inject=None, lds_scan_poke=None) -> List[Check]:
     given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.ops import cuframe
 
@@ -449,7 +454,7 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
             extra["atomics"] = True
             if atomics_inject is not None:
                 extra["atomics_inject"] = atomics_inject
-        for scan in cuframe.registry():
+        for scan in cuframe.scans():
             if given[scan.stem]:
                 extra[scan.stem] = True
                 for name in scan.controls:     # the CU scan's are not among the parameters

@@ -1,5 +1,5 @@
 // gm_cuscan_frame.h — the frame the per-CU scans share (gm_cuscan.hip, gm_mfmascan.hip,
-// gm_lanescan.hip, gm_cachescan.hip): where a
+// gm_lanescan.hip, gm_cachescan.hip, gm_ldsscan.hip): where a
 // block runs, the result table, the compare of one test's signature with the host's table, the
 // block-outcome reduction, the round loop and the decode into gm_cuscan_cu_t.
 //

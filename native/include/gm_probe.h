@@ -730,6 +730,132 @@ int gm_probe_cachescan_kernel_info(int* num_regs, int* scratch_bytes, int* icach
 int gm_probe_cachescan_geometry(uint32_t* seg_bytes, uint32_t* l1_hit_bytes, uint32_t* table_bytes,
                                 uint32_t* icache_steps);
 
+// ------------------------------------------------------------------ LDS scan
+// The CU scan's frame a fifth time, around what sits between a lane and the cells of the CU's
+// LDS (the CU scan's `lds` march proves that each cell holds a value, with 32- and 128-bit plain
+// accesses only). Five tests of 4 signature words per thread t (wave w = t / 64, lane l = t %
+// 64); the code is gm_ldsscan_ref.h. H is the CU scan's hash; fold(s, v) = rotl32(s, 5) + v;
+// P(id, r, p, a) = H(id, (8 r + p) * 65536 + a) is word a of pass p's image in round r;
+// perm(j, n, s, o) = (j s + o) % n with s odd and not a multiple of 5 (every n here is 2^k * 5),
+// and j(i, q) = 256 i + (t + 64 q) % 256 is thread t's index in step i, q waves on.
+//
+//   bit  name    per unit of iters
+//     1  width   1 round of the passes below
+//     2  atomic  1 round: initial values, the three phases, the final values
+//     4  bank    1 fill, 1 pass of 32-bit reads, 1 of 64-bit reads, 24 broadcast reads
+//     8  tr16    1 fill and 240 transposing reads per thread
+//    16  dma     1 load of all 160 KiB from the arena and its read-back
+//
+// width. s0..s3 = 0; per round r < iters, every pass touching each cell of the LDS once:
+//   1. 8-bit stores: word a = perm(j(i,0), 40960, 12347, 7), i < 160: the four bytes of
+//      P(0x500, r, 0, a), one ds_write_b8 each; barrier
+//   2. halfword perm(j(i,1), 81920, 20483, 5), i < 320: zero-extended where i is even,
+//      sign-extended where odd; then word perm(j(i,2), 40960, 6151, 3), i < 160; all into s0; barrier
+//   3. 16-bit stores: word perm(j(i,0), 40960, 4099, 11): the two halves of P(0x500, r, 1, a); barrier
+//   4. byte perm(j(i,1), 163840, 16411, 1), i < 640, zero- / sign-extended by i's parity; then the
+//      8-byte cell perm(j(i,3), 20480, 8209, 9), i < 80, as one 64-bit load (low word, high
+//      word); all into s1; barrier
+//   5. 64-bit stores: cell perm(j(i,0), 20480, 6163, 13), words P(0x500, r, 2, .); barrier
+//   6. ds_read2_b32: pair q = perm(j(i,1), 20480, 3079, 17), words x = 64 (q / 32) + q % 32 and
+//      x + 32, into s2; barrier
+//   7. 96-bit stores: 16-byte slot perm(j(i,0), 10240, 3083, 19), i < 40, its first three words
+//      P(0x500, r, 3, .); ds_write2_b32: pair q = perm(j(i,2), 5120, 1543, 23), i < 20, the last
+//      words of slots 16 (q / 8) + q % 8 and that + 8 (32 words apart); barrier
+//   8. ds_read2st64_b32: pair q = perm(j(i,3), 20480, 12301, 29), words x = 128 (q / 64) + q % 64
+//      and x + 64, into s2; barrier
+//   9. partial overwrite: word a = perm(j(i,0), 40960, 10243, 31), v = P(0x500, r, 4, a): byte
+//      v[7:0] to byte (v >> 8) & 3 of the word, then halfword v[31:16] to halfword (v >> 10) & 1;
+//      barrier; word perm(j(i,1), 40960, 14341, 37) into s3; barrier
+//
+// atomic. A table of GM_LDSSCAN_A_TABLE_WORDS words at the start of the LDS. No signature word
+// depends on the order in which lanes or waves reach a word: a returned old value is folded only
+// where one thread alone touches the word, contended words are folded as final values after a
+// barrier, and every contended operation commutes. Per round r: word a starts as I(r, a) =
+// H(0x510, 8192 r + a) (as float(I & 1023) where f32 is added, 0 for the tickets); barrier. The
+// operand of thread t, step s of slot k is O = H(0x511, ((128 r + k) * 4 + s) * 256 + t).
+//   (a) private, word 256 k + t for the 13 32-bit kinds k (add, sub, inc, dec, min and max signed
+//       and unsigned, and, or, xor, exchange, compare-and-swap), 8-byte word 3328 + 2 (256 k + t)
+//       for the 64-bit kinds (add, signed min, unsigned max, compare-and-swap; slots 16 + 2 k and
+//       + 1 for the high half), word 5376 + t for f32 add (slot 24, addend float(O & 15)): two
+//       returning operations each, every old value into s0. inc and dec wrap at (O & 7) + 1; and
+//       takes O | rotl32(O, 11), or takes O & rotl32(O, 11); compare-and-swap compares with the
+//       initial value in step 0 (it swaps) and with ~O of step 0 in step 1 (it does not).
+//   (b) contended, groups of 24 words from 5632: group 0 for all 256 threads (slots 32 + word),
+//       group 1 + w for the 64 lanes of wave w (slots 64 + word). Words 0, 2, 4, 6: 64-bit add,
+//       signed min, unsigned max, add by a compare-and-swap loop; 8..18: add, sub, min and max
+//       signed and unsigned, and, or, xor, add by a compare-and-swap loop, f32 add. No return is
+//       used. A compare-and-swap loop runs at most 256 tries; the give-ups (0: each failed try is
+//       caused by one of at most 255 successes of others) are counted.
+//   (c) tickets: 4 times, ticket = returning add of 1 to word 5752, then atomic or of bit
+//       ticket % 32 into word 5760 + (ticket / 32) % 32. The ticket is used, never folded.
+//   barrier; s1 = the thread's private words; s2 = words 0..18 of group 0, of group 1 + w, then
+//   the give-ups; s3 = the counter (1024) and the 32 bitmap words (all ones); barrier.
+//
+// bank. The LDS as ten chunks of 4096 words. Wave-instruction g = 4 i + (w + q) % 4 of a pass
+// walks chunk u = g / 64 at stride 2^k words, k = (u + r + shift) % 7: lane l of instruction m =
+// g % 64 takes n = 64 m + (l + m) % 64 and word 4096 u + (n % (4096 >> k)) * 2^k + n / (4096 >>
+// k). Per round: 32-bit writes of P(0x520, r, 0, a) (q = 0, shift 0; a permutation, so no two
+// lanes share a word); barrier; 32-bit reads (q = 1, shift 3) into s0; 64-bit reads of 8-byte
+// elements, chunks of 2048 elements, g = 4 i + (w + 2) % 4 < 320, u = g / 32, m = g % 32, k = (u
+// + r) % 6 (low word into s1, high into s2); broadcasts, 8 instructions g = 4 i + w each: all
+// lanes at word ((g + 32 r) * 1237 + 5) % 40960, each half h at (((g + 32 r) * 2 + h) * 3571 + 9)
+// % 40960, lanes l and l + 16 at (((g + 32 r) * 32 + l % 16 + 16 (l / 32)) * 12347 + 13) % 40960,
+// into s3; barrier. By the bank rule (32-bit: (a / 4) % 32, 64-bit: (a / 4) % 64, per 32-lane
+// half) every conflict degree 1, 2, 4, 8, 16, 32 occurs and every lane reads from every bank.
+//
+// tr16. Per round: 128-bit writes of P(0x530, r, 0, .), thread t the elements 256 k + t; barrier.
+// For the row strides S_k = 32, 72, 264 bytes and i < 80: the 16-lane group G = t / 16 reads
+// block n = 16 i + G at origin U_k ((4099 n + 17 k + 131 r) % N_k), N_k = (163840 - 3 S_k - 32) /
+// U_k + 1, U_k = 128, 8, 8 (at stride 32 the 1280 blocks tile the LDS); lane 4 q + p of the group supplies origin + q S_k + 8 p, and lane c receives elements
+// (row 0..3, column c): lo = rows 0, 1, hi = rows 2, 3. s_k = fold(fold(s_k, lo), hi); s3 =
+// fold(s3, lo ^ rotl32(hi, 13)); barrier.
+//
+// dma. The arena is 160 KiB of device memory, word a = P(0x540, 0, 0, a), shared by all blocks
+// and read only. Per round wave w moves chunk c = 4 i + w (1 KiB), i < 40, to chunk d = (37 c + 11
+// r + 3) % 160 of the LDS: where c + r is even with one global_load_lds_dwordx4 (lane l: the 16
+// bytes of slot (l + rho) % 64, rho = (7 c + r) % 64, to d's bytes 16 l ...), where odd with four
+// global_load_lds_dword (sub-chunk j: word (l + rho) % 64 of it to word l of sub-chunk (j + 1) %
+// 4). s_waitcnt vmcnt(0); barrier; every word of the LDS is read back by the wave after the one
+// that loaded it: s0 = fold(s0, g); s1 = rotl32(s1, 7) ^ g; s2 += g; s3 += (g != the arena's
+// pattern there); barrier.
+//
+// Not covered: the 4-, 6- and 8-bit transposing reads, cross-lane permutes (the lane scan has
+// them), any judgment of speed or of conflict cycles.
+//
+// The records, the injection, the per-CU entries and the result are the CU scan's, with `test`
+// and `tests_failed` holding GM_LDSSCAN_* bits; 1 <= iters <= GM_LDSSCAN_MAX_ITERS. Every
+// argument check comes before any HIP call.
+//
+// Second negative control, through the real detection path: for width, bank and tr16, after the
+// test's first fill and barrier, thread 0 of every block XORs `mask` into word `word_offset` of
+// the LDS, before the barrier that precedes the reads; for dma the host flips that word of the
+// arena. The scan still compares with the table of a clean run; gm_probe_ldsscan_expected with
+// the poke gives the exact signature of the poked run. `atomic` has no data to poke.
+// hipErrorInvalidValue for atomic, a test that is not selected, an offset of 40960 or more, or
+// mask == 0.
+typedef struct gm_ldsscan_poke {
+  uint32_t test, word_offset, mask;
+} gm_ldsscan_poke_t;
+
+// The expected table of `test`, in a run with `poke` (null: none). A poke of another test leaves
+// it alone. Host only, needs no GPU.
+int gm_probe_ldsscan_expected(uint32_t test, uint64_t seed, uint32_t iters,
+                              const gm_ldsscan_poke_t* poke, uint32_t* out);
+// One block, raw, with an arena of its own. It returns after the block has run.
+int gm_probe_ldsscan_signature(uint32_t test, uint64_t seed, uint32_t iters,
+                               const gm_ldsscan_poke_t* poke, uint32_t* dev_out,
+                               uint32_t* dev_where, void* stream);
+// The scan. `inject` and `poke` may be null.
+int gm_probe_ldsscan(int dev, uint32_t tests_mask, uint32_t iters, uint64_t seed, int min_rounds,
+                     int max_rounds, const gm_cuscan_inject_t* inject, const gm_ldsscan_poke_t* poke,
+                     gm_cuscan_result_t* out, gm_cuscan_cu_t* cus, int cus_cap, int* n_cus);
+// numRegs and localSizeBytes of the scan kernel from hipFuncGetAttributes on the current device.
+int gm_probe_ldsscan_kernel_info(int* num_regs, int* scratch_bytes);
+// The LDS and the arena in bytes, the atomic table in words, the three tr16 row strides in bytes.
+// Host only.
+int gm_probe_ldsscan_geometry(uint32_t* lds_bytes, uint32_t* arena_bytes,
+                              uint32_t* atomic_table_words, uint32_t tr16_strides[3]);
+
 // ------------------------------------------------------------------ host link (PCIe) test
 // Moves checked bytes between pinned host memory and the GPU, in both directions, by the copy
 // engines (hipMemcpyAsync) and by kernels that read and write host memory through its device
