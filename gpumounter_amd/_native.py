@@ -280,6 +280,34 @@ class LdsscanPoke(C.Structure):       # gm_ldsscan_poke_t
     _fields_ = [("test", C.c_uint32), ("word_offset", C.c_uint32), ("mask", C.c_uint32)]
 
 
+BURNIN_LOG_CAP = 1024         # native/include/gm_probe.h GM_BURNIN_LOG_CAP
+BURNIN_MAX_RECORDS = 16       # GM_BURNIN_MAX_RECORDS
+
+
+class BurninEvent(C.Structure):       # gm_burnin_event_t
+    _fields_ = [("iteration", C.c_uint32), ("tile", C.c_uint32), ("worker", C.c_uint32),
+                ("reference", C.c_uint32), ("words", C.c_uint32)]
+
+
+class BurninInject(C.Structure):      # gm_burnin_inject_t
+    _fields_ = [("id", C.c_uint32), ("mask", C.c_uint32), ("first", C.c_uint32)]
+
+
+class BurninBlamed(C.Structure):      # gm_burnin_blamed_t
+    _fields_ = [("id", C.c_uint32), ("events", C.c_uint32), ("as_worker", C.c_uint32),
+                ("as_reference", C.c_uint32), ("words", C.c_uint64)]
+
+
+class BurninAttr(C.Structure):        # gm_burnin_attr_t
+    _fields_ = [("tiles", C.c_uint32), ("grid", C.c_uint32), ("step", C.c_uint32),
+                ("rotations", C.c_uint32), ("cus_seen", C.c_uint32),
+                ("tiles_moved", C.c_uint32), ("tiles_exonerated", C.c_uint32),
+                ("logged", C.c_uint32), ("log_overflow", C.c_uint32), ("first_id", C.c_uint32),
+                ("inject_id", C.c_uint32), ("n_blamed", C.c_uint32),
+                ("records_filled", C.c_uint32), ("events", C.c_uint64),
+                ("records", BurninEvent * BURNIN_MAX_RECORDS)]
+
+
 HOSTLINK_LEGS = 6             # native/include/gm_probe.h GM_HOSTLINK_LEGS
 HOSTLINK_MAX_RECORDS = 16     # GM_HOSTLINK_MAX_RECORDS
 HOSTLINK_MAX_BLOCKS = 1024    # GM_HOSTLINK_MAX_BLOCKS
@@ -454,6 +482,21 @@ def probe() -> C.CDLL:
         lib.gm_probe_mxgemm_kernel_info.argtypes = [C.c_int, C.POINTER(C.c_int),
                                                     C.POINTER(C.c_int)]
         lib.gm_probe_mx_burn_in_flip.argtypes = [C.c_int] + lib.gm_probe_burn_in_flip.argtypes
+        lib.gm_probe_burn_in_blame.argtypes = [C.POINTER(BurninEvent), C.c_int64,
+                                               C.POINTER(C.c_uint8), C.c_int,
+                                               C.POINTER(BurninAttr), C.POINTER(BurninBlamed),
+                                               C.c_int]
+        lib.gm_probe_burn_in_tile_map.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 3
+        traced = [C.c_int, C.c_void_p, C.POINTER(BurninInject), C.c_void_p]
+        lib.gm_probe_gemm_nt_traced.argtypes = lib.gm_probe_gemm_nt.argtypes[:-1] + traced
+        lib.gm_probe_mxgemm_nt_traced.argtypes = lib.gm_probe_mxgemm_nt.argtypes[:-1] + traced
+        lib.gm_probe_gemm_nt_traced_info.argtypes = [C.POINTER(C.c_int)] * 2
+        lib.gm_probe_mxgemm_nt_traced_info.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 2
+        lib.gm_probe_burn_in_attr.argtypes = (
+            lib.gm_probe_burn_in_flip.argtypes[:6] + [C.POINTER(BurninInject)] +
+            lib.gm_probe_burn_in_flip.argtypes[6:] +
+            [C.POINTER(BurninAttr), C.POINTER(BurninBlamed), C.c_int])
+        lib.gm_probe_mx_burn_in_attr.argtypes = [C.c_int] + lib.gm_probe_burn_in_attr.argtypes
         lib.gm_probe_lanescan_expected.argtypes = lib.gm_probe_cuscan_expected.argtypes
         lib.gm_probe_lanescan_lanes.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int),
                                                 C.POINTER(C.c_uint32)]

@@ -7,6 +7,8 @@
     python -m gpumounter_amd probe     [--bdf 0000:05:00.0] [--full] [--burn-in 60]  # gfx950 kernels
                                        [--burn-in-flip ELEM:MASK]            # its negative control
                                        [--burn-in-format bf16,mxfp8,mxfp4]   # also on the MX pipe
+                                       [--burn-in-attribute]                 # rotate tiles, name CUs
+                                       [--burn-in-inject ID|first:MASK]      # its negative control
                                        [--memtest [SIZE]] [--memtest-passes N]
                                        [--memtest-patterns addr,solid,checker,walk,random]
                                        [--memtest-flip OFFSET:MASK]          # HBM pattern test
@@ -219,6 +221,38 @@ def _add_burn_in_format(p) -> None:
                    help="with --burn-in: the burn-in's formats, of bf16,mxfp8,mxfp4 (default "
                         "bf16); each runs for SECONDS, the block-scaled ones as a bit-checked "
                         "fp8 / fp4 GEMM on the MX matrix pipe")
+    p.add_argument("--burn-in-attribute", action="store_true",
+                   help="with --burn-in: rotate the GEMM's tiles over the blocks from one "
+                        "iteration to the next, so other XCDs and CUs recompute every tile, "
+                        "record the CU of every block and name the units behind a mismatch")
+    p.add_argument("--burn-in-inject", type=_burn_in_inject, default=None, metavar="ID|first:MASK",
+                   help="with --burn-in-attribute: negative control: every block on that CU "
+                        "(first: the one that computed tile 0 in the warm-up) XORs MASK into "
+                        "one element of its tile, in the reference too; the burn-in must fail "
+                        "and name that unit alone")
+
+
+def _burn_in_inject(text):
+    """argparse type for --burn-in-inject: the parser in ops.probe, its refusal a usage error."""
+    from gpumounter_amd.ops import probe
+    try:
+        return probe.parse_burn_in_inject(text)
+    except probe.ProbeError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def _burn_in_usage(args, tool: str) -> str:
+    """What is wrong with the burn-in's options, or ""."""
+    older = [("--burn-in-flip", args.burn_in_flip), ("--burn-in-format", args.burn_in_format)]
+    if tool == "doctor":              # it has always named the format first
+        older.reverse()
+    for option, value in older + [("--burn-in-attribute", args.burn_in_attribute),
+                                  ("--burn-in-inject", args.burn_in_inject)]:
+        if value and not args.burn_in:
+            return f"{tool}: {option} needs --burn-in SECONDS"
+    if args.burn_in_inject and not args.burn_in_attribute:
+        return f"{tool}: --burn-in-inject needs --burn-in-attribute"
+    return ""
 
 
 def _atomics_arg(kind):
@@ -371,12 +405,10 @@ def _add_memtest_size(p, what: str) -> None:
 def cmd_probe(args) -> int:
     from gpumounter_amd.ops import probe
 
-    if args.burn_in_flip and not args.burn_in:
-        print("probe: --burn-in-flip needs --burn-in SECONDS", file=sys.stderr)
+    error = _burn_in_usage(args, "probe")
+    if error:
+        print(error, file=sys.stderr)
         return 2                      # a usage error, not a failed burn-in (exit 1)
-    if args.burn_in_format and not args.burn_in:
-        print("probe: --burn-in-format needs --burn-in SECONDS", file=sys.stderr)
-        return 2
     cu, *later = _scans()             # the CU scan: before the host-link and atomics tests
     error = _scan_usage(cu, args, "probe")
     if error:
@@ -450,8 +482,9 @@ def cmd_probe(args) -> int:
         for r in res:
             for fmt in args.burn_in_format or ("bf16",):
                 key = mxgemm.burn_in_key(fmt)
-                r[key] = mxgemm.run_burn_in(r["device"], args.burn_in, fmt,
-                                            _flips=args.burn_in_flip)
+                r[key] = mxgemm.run_burn_in(
+                    r["device"], args.burn_in, fmt, _flips=args.burn_in_flip,
+                    **mxgemm.attribute_kwargs(args.burn_in_attribute, args.burn_in_inject))
                 bad |= not r[key]["ok"]
     if args.memtest is not None:
         from gpumounter_amd.ops import memtest
@@ -645,11 +678,14 @@ def cmd_doctor(args) -> int:
     if args.atomics_inject and not args.atomics:
         print("doctor: --atomics-inject needs --atomics", file=sys.stderr)
         return 2
-    for option, value, name in (("--burn-in-format", args.burn_in_format, "burn_in_formats"),
-                                ("--burn-in-flip", args.burn_in_flip, "burn_in_flip")):
-        if value and not args.burn_in:
-            print(f"doctor: {option} needs --burn-in SECONDS", file=sys.stderr)
-            return 2
+    error = _burn_in_usage(args, "doctor")
+    if error:
+        print(error, file=sys.stderr)
+        return 2
+    for value, name in ((args.burn_in_format, "burn_in_formats"),
+                        (args.burn_in_flip, "burn_in_flip"),
+                        (args.burn_in_attribute, "burn_in_attribute"),
+                        (args.burn_in_inject, "burn_in_inject")):
         if value:
             extra[name] = value
     if args.atomics:

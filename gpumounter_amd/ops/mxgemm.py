@@ -171,16 +171,61 @@ def kernel_info(fmt: str = "mxfp8") -> Dict[str, int]:
     return {"num_regs": regs.value, "scratch_bytes": scratch.value}
 
 
+def gemm_nt_traced(fmt: str, a, sa, bt, sb, r: int = 0, out=None, _inject=None, stream=None):
+    """:func:`gemm_nt` through the attributed burn-in's kernel at rotation ``r``: (C,
+    cu_of_tile), as :func:`probe.gemm_nt_traced`. Asynchronous."""
+    import torch
+
+    _fmt(fmt)
+    for t, what in ((a, "A"), (sa, "sA"), (bt, "Bt"), (sb, "sB")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ProbeError(f"mxgemm: {what} must be a 2-D uint8 torch tensor")
+    m, n, k = int(a.shape[0]), int(bt.shape[0]), int(sa.shape[1]) * BLOCK
+    check_shape(fmt, m, n, k)
+    _operand(a, "A", m, row_bytes(fmt, k))
+    _operand(bt, "Bt", n, row_bytes(fmt, k))
+    _operand(sa, "sA", m, k // BLOCK)
+    _operand(sb, "sB", n, k // BLOCK)
+    if len({t.device for t in (a, sa, bt, sb)}) != 1:
+        raise ProbeError("mxgemm: the operands are on different devices")
+    grid = (m // TILE_MN) * (n // TILE_MN)
+    if not isinstance(r, int) or isinstance(r, bool) or not 0 <= r < grid:
+        raise ProbeError(f"mxgemm traced: rotation {r!r} is not in [0, {grid})")
+    inj = probe._burn_in_inject(_inject, True)
+    if inj is not None and inj.first:
+        raise ProbeError("mxgemm traced: one GEMM has no warm-up to take 'first' from")
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
+    elif (not isinstance(out, torch.Tensor) or out.shape != (m, n) or out.dtype != torch.bfloat16
+          or not out.is_contiguous() or out.device != a.device):
+        raise ProbeError(f"mxgemm: out must be a contiguous bf16 [{m}, {n}] tensor on {a.device}")
+    cus = torch.full((grid,), -1, dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        _check(_native.probe().gm_probe_mxgemm_nt_traced(
+            FORMAT_CODE[fmt], a.data_ptr(), sa.data_ptr(), bt.data_ptr(), sb.data_ptr(),
+            out.data_ptr(), m, n, k, r, cus.data_ptr(), C.byref(inj) if inj else None,
+            probe._stream_of(a, stream)), "mxgemm traced")
+    return out, cus
+
+
 def burn_in(dev: int, seconds: float, fmt: str, n: int = 8192,
-            _flips: Optional[Sequence[Tuple[int, int]]] = None) -> Dict:
+            _flips: Optional[Sequence[Tuple[int, int]]] = None, attribute: bool = False,
+            _inject=None) -> Dict:
     """:func:`probe.burn_in` on the block-scaled pipe: back-to-back n³ GEMMs of ``fmt`` on
     random-class operands for ``seconds``, each result compared bit for bit with the first.
     Returns :func:`probe.burn_in`'s dict plus ``"format"``; ``tflops`` counts 2 n³ per GEMM.
-    ``_flips`` as there: bf16 elements of the n × n reference result."""
+    ``_flips`` as there: bf16 elements of the n × n reference result. ``attribute`` and
+    ``_inject`` as there too: the rotated tile map, the CU of every block and ``"attribution"``."""
     check_shape(fmt, n, n, n)
     if not isinstance(seconds, (int, float)) or isinstance(seconds, bool) or not seconds > 0:
         raise ProbeError(f"mx burn-in: seconds = {seconds!r} is not a positive number")
     elems, fe, fm = probe._burn_in_flips(_flips, n)
+    inj = probe._burn_in_inject(_inject, attribute)
+    if attribute:
+        out = probe._run_attributed(f"{fmt} burn-in", _native.probe().gm_probe_mx_burn_in_attr,
+                                    (dev, FORMAT_CODE[fmt]), dev, n, seconds, elems, fe, fm, inj)
+        out["format"] = fmt
+        return out
     tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
     _check(_native.probe().gm_probe_mx_burn_in_flip(dev, FORMAT_CODE[fmt], n, seconds,
                                                     len(elems), fe, fm, C.byref(tf),
@@ -209,9 +254,24 @@ def burn_in_key(fmt: str) -> str:
     return "burn_in" if fmt == "bf16" else f"burn_in_{fmt}"
 
 
-def run_burn_in(dev: int, seconds: float, fmt: str, _flips=None) -> Dict:
-    """One chosen format's burn-in at the default size: what probe, doctor and validate run."""
-    flips = {} if _flips is None else {"_flips": _flips}
+def run_burn_in(dev: int, seconds: float, fmt: str, _flips=None, attribute: bool = False,
+                _inject=None) -> Dict:
+    """One chosen format's burn-in at the default size: what probe, doctor and validate run.
+    Only what was asked for is handed down: no keyword for a control that is not given."""
+    more = {} if _flips is None else {"_flips": _flips}
+    if attribute:
+        more["attribute"] = True
+    if _inject is not None:
+        more["_inject"] = _inject
     if fmt == "bf16":
-        return probe.burn_in(dev, seconds, **flips)
-    return burn_in(dev, seconds, fmt, **flips)
+        return probe.burn_in(dev, seconds, **more)
+    return burn_in(dev, seconds, fmt, **more)
+
+
+def attribute_kwargs(attribute, inject) -> Dict:
+    """The keyword arguments :func:`run_burn_in` takes for ``--burn-in-attribute`` and
+    ``--burn-in-inject``: none where neither is given."""
+    more = {"attribute": True} if attribute else {}
+    if inject is not None:
+        more["_inject"] = inject
+    return more

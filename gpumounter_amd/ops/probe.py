@@ -262,15 +262,221 @@ def _burn_in_report(dev: int, n: int, seconds: float, elems, tf, bad, it) -> Dic
     return out
 
 
+BURN_IN_FIRST = "first"       # an injection into the CU that computed tile 0 in the warm-up
+BURN_IN_TILE = 256
+
+
+def _burn_in_id(v, what: str) -> int:
+    if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < _native.CUSCAN_IDS:
+        raise ProbeError(f"burn-in: {what} {v!r} is not an integer in [0, "
+                         f"{_native.CUSCAN_IDS})")
+    return v
+
+
+def parse_burn_in_inject(text) -> Tuple:
+    """``"ID:MASK"`` or ``"first:MASK"`` (Python integer literals, e.g. ``0x123:0x1``) → (a
+    12-bit CU id or ``"first"``, a nonzero 16-bit XOR mask): the attributed burn-in's injection."""
+    try:
+        cu_id, mask = (p.strip() for p in str(text).split(":"))
+        cu_id = BURN_IN_FIRST if cu_id.lower() == BURN_IN_FIRST else int(cu_id, 0)
+        mask = int(mask, 0)
+    except ValueError:
+        raise ProbeError(f"burn-in: cannot read {text!r} as ID|first:MASK") from None
+    _burn_in_inject((cu_id, mask), True)
+    return cu_id, mask
+
+
+def _burn_in_inject(_inject, attribute: bool) -> Optional[_native.BurninInject]:
+    """The attributed burn-ins' injection, checked: None, or the native struct."""
+    if _inject is None:
+        return None
+    if not attribute:
+        raise ProbeError("burn-in: an injection needs attribute=True (it is a statement about a "
+                         "CU, and only the attributed burn-in knows the CUs)")
+    try:
+        cu_id, mask = _inject
+    except (TypeError, ValueError):
+        raise ProbeError(f"burn-in: injection {_inject!r} is not (id or 'first', mask)") from None
+    if cu_id != BURN_IN_FIRST:
+        _burn_in_id(cu_id, "injection id")
+    if not isinstance(mask, int) or isinstance(mask, bool) or not 0 < mask < 1 << 16:
+        raise ProbeError(f"burn-in: injection mask {mask!r} is not a nonzero 16-bit integer")
+    first = cu_id == BURN_IN_FIRST
+    return _native.BurninInject(0 if first else cu_id, mask, int(first))
+
+
+def _blamed_units(blamed, n: int) -> List[Dict]:
+    from gpumounter_amd.ops import cuframe
+
+    return [{"id": b.id, **cuframe.decode_id(b.id), "events": b.events, "words": b.words,
+             "as_worker": b.as_worker, "as_reference": b.as_reference}
+            for b in blamed[:min(n, len(blamed))]]
+
+
+def _first_events(attr) -> List[Dict]:
+    return [{"iteration": e.iteration, "tile": e.tile, "worker": e.worker,
+             "reference": e.reference, "words": e.words}
+            for e in attr.records[:attr.records_filled]]
+
+
+def _attribution(attr, blamed) -> Dict:
+    """The ``attribution`` dict of an attributed burn-in from the C structures."""
+    units = _blamed_units(blamed, attr.n_blamed)
+    out = {"tiles": attr.tiles, "grid": attr.grid, "step": attr.step,
+           "rotations": attr.rotations, "cus_seen": attr.cus_seen,
+           "tiles_moved": attr.tiles_moved, "tiles_exonerated": attr.tiles_exonerated,
+           "events": attr.events, "logged": attr.logged,
+           "log_overflow": bool(attr.log_overflow), "first_id": attr.first_id,
+           "blamed": units, "first_events": _first_events(attr)}
+    if attr.inject_id != _native.CUSCAN_ANY:
+        out["inject_id"] = attr.inject_id
+    if attr.log_overflow:
+        out["note"] = (f"{attr.events - attr.logged} of the {attr.events} events were counted "
+                       f"but not logged: only the logged ones are blamed")
+    return out
+
+
+def _run_attributed(what: str, entry, lead: tuple, dev: int, n: int, seconds: float, elems,
+                    fe, fm, inj) -> Dict:
+    """One attributed burn-in through ``entry`` (``lead``: what it takes before ``n``)."""
+    tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
+    attr = _native.BurninAttr()
+    blamed = (_native.BurninBlamed * _native.BURNIN_LOG_CAP)()
+    _check(entry(*lead, n, seconds, len(elems), fe, fm, C.byref(inj) if inj else None,
+                 C.byref(tf), C.byref(bad), C.byref(it), C.byref(attr), blamed, len(blamed)),
+           what)
+    out = _burn_in_report(dev, n, seconds, elems, tf, bad, it)
+    out["attribution"] = _attribution(attr, blamed)
+    return out
+
+
+def describe_blamed(result: Dict) -> str:
+    """One line naming the units an attributed burn-in blames (the first four, then how many
+    more), in the words the scans use, for ``doctor``."""
+    blamed = result["attribution"]["blamed"]
+    text = "; ".join(
+        f"xcc {b['xcc']} se {b['se']} sh {b['sh']} cu {b['cu']} (id {b['id']:#05x}) "
+        + " + ".join(f"{b[k]} as {k[3:]}" for k in ("as_worker", "as_reference") if b[k])
+        for b in blamed[:4])
+    return text + (f"; and {len(blamed) - 4} more" if len(blamed) > 4 else "")
+
+
+def burn_in_tile_map(n: int, r: int = 0) -> Tuple[List[int], int]:
+    """Host only: (the tile, row-major over the (n / 256)² tiles, that each block of the
+    burn-in GEMM's grid computes at rotation ``r``; the rotation's step for that grid)."""
+    if not isinstance(n, int) or isinstance(n, bool) or n <= 0 or n % BURN_IN_TILE:
+        raise ProbeError(f"burn-in: n = {n!r} is not a positive multiple of {BURN_IN_TILE}")
+    grid = (n // BURN_IN_TILE) ** 2
+    if not isinstance(r, int) or isinstance(r, bool) or not 0 <= r < grid:
+        raise ProbeError(f"burn-in: rotation {r!r} is not in [0, {grid})")
+    tm, tn, step, tiles = C.c_int(0), C.c_int(0), C.c_int(0), []
+    for b in range(grid):
+        _check(_native.probe().gm_probe_burn_in_tile_map(n, n, b, r, C.byref(tm), C.byref(tn),
+                                                         C.byref(step)), "burn-in tile map")
+        tiles.append(tm.value * (n // BURN_IN_TILE) + tn.value)
+    return tiles, step.value
+
+
+def burn_in_blame(events: Sequence[Tuple[int, int, int, int, int]], exonerated: Sequence,
+                  counted: Optional[int] = None) -> Dict:
+    """Host only: the attributed burn-in's blame rule over a log of (iteration, tile, worker id,
+    reference id, words) and one exonerated flag per tile. ``counted``: how many events the run
+    counted, where that is more than the log holds."""
+    tiles = len(exonerated)
+    if tiles == 0:
+        raise ProbeError("burn-in blame: no tiles")
+    for e in events:
+        if len(e) != 5 or not all(isinstance(v, int) and 0 <= v < 1 << 32 for v in e):
+            raise ProbeError(f"burn-in blame: event {e!r} is not five 32-bit integers")
+        if e[1] >= tiles:
+            raise ProbeError(f"burn-in blame: event {e!r} at a tile outside the {tiles}")
+        _burn_in_id(e[2], "worker id"), _burn_in_id(e[3], "reference id")
+    counted = len(events) if counted is None else counted
+    if not isinstance(counted, int) or counted < len(events):
+        raise ProbeError(f"burn-in blame: counted = {counted!r} is below the log's length")
+    if len(events) < min(counted, _native.BURNIN_LOG_CAP):
+        raise ProbeError("burn-in blame: the log is shorter than what was counted and fits")
+    ev = (_native.BurninEvent * max(1, len(events)))(*[_native.BurninEvent(*e) for e in events])
+    ex = (C.c_uint8 * tiles)(*[1 if x else 0 for x in exonerated])
+    attr = _native.BurninAttr()
+    blamed = (_native.BurninBlamed * _native.BURNIN_LOG_CAP)()
+    _check(_native.probe().gm_probe_burn_in_blame(ev, counted, ex, tiles, C.byref(attr), blamed,
+                                                  len(blamed)), "burn-in blame")
+    units = _blamed_units(blamed, attr.n_blamed)
+    return {"events": attr.events, "logged": attr.logged,
+            "log_overflow": bool(attr.log_overflow), "tiles_exonerated": attr.tiles_exonerated,
+            "blamed": units, "first_events": _first_events(attr)}
+
+
+def gemm_nt_traced(a, bt, r: int = 0, out=None, _inject=None, stream=None):
+    """:func:`gemm_nt` through the attributed burn-in's kernel at rotation ``r``: (C, cu_of_tile),
+    ``cu_of_tile`` an int32 device tensor with the 12-bit id of the CU that computed each tile,
+    row-major over the tiles. ``_inject=(id, mask)``: blocks on that CU flip element (0, 0) of
+    their tile. Asynchronous."""
+    import torch
+
+    if a.dtype != torch.bfloat16 or bt.dtype != torch.bfloat16:
+        raise ProbeError("gemm_nt_traced expects bf16 inputs")
+    if not (a.is_contiguous() and bt.is_contiguous()):
+        raise ProbeError("gemm_nt_traced expects contiguous inputs")
+    m, k = a.shape
+    n, k2 = bt.shape
+    if k != k2 or m % 256 or n % 256 or k % 64:
+        raise ProbeError(f"unsupported shape A{tuple(a.shape)} Bt{tuple(bt.shape)}")
+    grid = (m // 256) * (n // 256)
+    if not isinstance(r, int) or isinstance(r, bool) or not 0 <= r < grid:
+        raise ProbeError(f"gemm_nt_traced: rotation {r!r} is not in [0, {grid})")
+    inj = _burn_in_inject(_inject, True)
+    if inj is not None and inj.first:
+        raise ProbeError("gemm_nt_traced: one GEMM has no warm-up to take 'first' from")
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
+    elif out.shape != (m, n) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise ProbeError("gemm_nt_traced: out must be a contiguous bf16 [M,N] tensor")
+    cus = torch.full((grid,), -1, dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        _check(_native.probe().gm_probe_gemm_nt_traced(
+            a.data_ptr(), bt.data_ptr(), out.data_ptr(), m, n, k, r, cus.data_ptr(),
+            C.byref(inj) if inj else None, _stream_of(a, stream)), "gemm_nt_traced")
+    return out, cus
+
+
+def traced_kernel_info(fmt: str = "bf16") -> Dict[str, int]:
+    """Registers and scratch bytes of a format's traced GEMM kernel: ``scratch_bytes`` must be
+    0, as for the plain kernels."""
+    from gpumounter_amd.ops import mxgemm
+
+    regs, scratch = C.c_int(0), C.c_int(0)
+    if fmt == "bf16":
+        rc = _native.probe().gm_probe_gemm_nt_traced_info(C.byref(regs), C.byref(scratch))
+    else:
+        rc = _native.probe().gm_probe_mxgemm_nt_traced_info(mxgemm._fmt(fmt), C.byref(regs),
+                                                            C.byref(scratch))
+    _check(rc, "traced kernel info")
+    return {"num_regs": regs.value, "scratch_bytes": scratch.value}
+
+
 def burn_in(dev: int, seconds: float = 10.0, n: int = 8192,
-            _flips: Optional[Sequence[Tuple[int, int]]] = None) -> Dict:
+            _flips: Optional[Sequence[Tuple[int, int]]] = None, attribute: bool = False,
+            _inject=None) -> Dict:
     """Sustained-load check of an attached GPU: back-to-back n³ bf16 GEMMs for ``seconds``,
     each compared bit-for-bit with the first result (the kernel is deterministic). Any
     ``mismatches`` means silent data corruption. ``tflops`` is the sustained rate, so
     throttling shows up as a low number. ``_flips=[(elem, mask), ...]`` is the negative control:
     those bf16 elements of the reference result are XORed with ``mask`` before the loop, so
-    every iteration must count each 16-byte word they touch."""
+    every iteration must count each 16-byte word they touch.
+
+    ``attribute=True`` rotates the block → tile map from one iteration to the next, so every
+    tile is recomputed by other blocks, XCDs and CUs than the reference's, records the CU of
+    every block and adds ``"attribution"``: what moved, and the units blamed for mismatches
+    (native/include/gm_probe.h, "attributed burn-in"). ``_inject=(id or "first", mask)`` is its
+    negative control: every block on that CU XORs ``mask`` into element (0, 0) of its tile, in
+    the reference too; ``"first"`` is the CU that computed tile 0 in the warm-up."""
     elems, fe, fm = _burn_in_flips(_flips, n)
+    inj = _burn_in_inject(_inject, attribute)
+    if attribute:
+        return _run_attributed("burn-in", _native.probe().gm_probe_burn_in_attr, (dev,), dev, n,
+                               seconds, elems, fe, fm, inj)
     tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
     _check(_native.probe().gm_probe_burn_in_flip(dev, n, seconds, len(elems), fe, fm,
                                                  C.byref(tf), C.byref(bad), C.byref(it)),

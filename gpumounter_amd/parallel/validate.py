@@ -122,6 +122,12 @@ def main(argv=None) -> int:
     ap.add_argument("--burn-in-flip", action="append", default=None, metavar="ELEM:MASK",
                     help="the burn-in's negative control, for every chosen format (see probe "
                          "--burn-in-flip); needs --burn-in")
+    ap.add_argument("--burn-in-attribute", action="store_true",
+                    help="the burn-in with its tiles rotated over the CUs, naming the units "
+                         "behind a mismatch (see probe --burn-in-attribute); needs --burn-in")
+    ap.add_argument("--burn-in-inject", default=None, metavar="ID|first:MASK",
+                    help="its negative control (see probe --burn-in-inject); needs "
+                         "--burn-in-attribute")
     ap.add_argument("--memtest", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the HBM pattern test on every GPU at once over SIZE bytes each "
                          "(64M, 8G; default: 90 %% of the free memory)")
@@ -167,6 +173,19 @@ def main(argv=None) -> int:
                 burn_in_flips = [_probe.parse_burn_in_flip(t) for t in args.burn_in_flip]
         except ProbeError as e:
             ap.error(str(e))
+    burn_in_more: Dict = {}           # the attributed mode's keywords, none unless asked for
+    if args.burn_in_attribute or args.burn_in_inject is not None:
+        from gpumounter_amd.ops import mxgemm, probe as _probe
+        if not args.burn_in:
+            ap.error("--burn-in-attribute and --burn-in-inject need --burn-in SECONDS")
+        if not args.burn_in_attribute:
+            ap.error("--burn-in-inject needs --burn-in-attribute")
+        try:
+            inject = (None if args.burn_in_inject is None
+                      else _probe.parse_burn_in_inject(args.burn_in_inject))
+        except ProbeError as e:
+            ap.error(str(e))
+        burn_in_more = mxgemm.attribute_kwargs(True, inject)
     atomics_inject = None
     if args.atomics_inject is not None:
         from gpumounter_amd.ops import atomics
@@ -227,7 +246,8 @@ def main(argv=None) -> int:
         for fmt in burn_in_formats:
             with ThreadPoolExecutor(max_workers=world) as ex:
                 burn = list(ex.map(lambda d: mxgemm.run_burn_in(d, args.burn_in, fmt,
-                                                                _flips=burn_in_flips),
+                                                                _flips=burn_in_flips,
+                                                                **burn_in_more),
                                    range(world)))
             report[mxgemm.burn_in_key(fmt)] = burn
             report["ok"] &= all(b["ok"] for b in burn)

@@ -305,7 +305,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                lane_scan_inject=None, cache_scan: bool = False,
                cache_scan_inject=None, cache_scan_poke=None,
                burn_in_formats=("bf16",), lds_scan: bool = False,
-               lds_scan_inject=None, lds_scan_poke=None) -> List[Check]:
+               lds_scan_inject=None, lds_scan_poke=None, burn_in_attribute: bool = False,
+               burn_in_inject=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked GEMM load per GPU, once per format in ``burn_in_formats`` (bf16, and the
@@ -313,7 +314,10 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     mismatching word fails the check and is named. With ``memtest_bytes`` also the HBM pattern
     test over that many bytes per GPU (negative: 90 % of what is free on it); ``memtest_flip``
     = (offset, mask) is its negative control, ``burn_in_flip`` = [(element, mask), ...] the
-    burn-in's (see :func:`probe.burn_in`). With ``cu_scan`` also the per-CU self-test
+    burn-in's (see :func:`probe.burn_in`). With ``burn_in_attribute`` the burn-ins rotate their
+    tiles over the CUs and a failing one names the units it blames, as the scans name theirs, with
+    their role and the format; ``burn_in_inject`` = (id or "first", mask) is that mode's negative
+    control. With ``cu_scan`` also the per-CU self-test
     (:func:`gpumounter_amd.ops.cuscan.scan`): a CU with a wrong word fails the check and is named;
     a scan that did not reach every CU is stated and does not fail it; ``cu_scan_inject`` is its
     negative control. With ``host_link_bytes`` also the host link (PCIe) test
@@ -367,11 +371,21 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                       f"(first launch {cold / 1e3:.0f} ms)")
             status = "ok" if arch == "gfx950" else "warn"
             for fmt in burn_in_formats if burn_in_s > 0 else ():
-                b = mxgemm.run_burn_in(d, burn_in_s, fmt, _flips=burn_in_flip)
+                b = mxgemm.run_burn_in(d, burn_in_s, fmt, _flips=burn_in_flip,
+                                       **mxgemm.attribute_kwargs(burn_in_attribute,
+                                                                 burn_in_inject))
                 detail += (f", burn-in {'' if fmt == 'bf16' else fmt + ' '}{b['seconds']:g} s "
                            f"{b['tflops']:.0f} TF/s {b['mismatches']} mismatching words")
+                if "attribution" in b:
+                    a = b["attribution"]
+                    detail += (f", {a['tiles']} tiles over {a['cus_seen']} CUs, "
+                               f"{a['tiles_moved']} moved")
                 if not b["ok"]:
                     detail += "" if fmt == "bf16" else f", failed: {fmt} burn-in"
+                    if "attribution" in b:
+                        detail += (f", {fmt} burn-in blames: {probe.describe_blamed(b)}"
+                                   + (" (log overflowed: only the logged events are blamed)"
+                                      if b["attribution"]["log_overflow"] else ""))
                     status = "fail"
             if memtest_bytes:
                 from gpumounter_amd.ops import memtest
@@ -436,7 +450,8 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         mfma_scan: bool = False, mfma_scan_inject=None, lane_scan: bool = False,
         lane_scan_inject=None, cache_scan: bool = False, cache_scan_inject=None,
         cache_scan_poke=None, burn_in_formats=None, burn_in_flip=None,
-        lds_scan: bool = False, lds_scan_inject=None, lds_scan_poke=None) -> List[Check]:
+        lds_scan: bool = False, lds_scan_inject=None, lds_scan_poke=None,
+        burn_in_attribute: bool = False, burn_in_inject=None) -> List[Check]:
     given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.ops import cuframe
 
@@ -448,6 +463,10 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
             extra["burn_in_formats"] = burn_in_formats
         if burn_in_flip is not None:
             extra["burn_in_flip"] = burn_in_flip
+        if burn_in_attribute:
+            extra["burn_in_attribute"] = True
+        if burn_in_inject is not None:
+            extra["burn_in_inject"] = burn_in_inject
         if host_link_bytes:
             extra["host_link_bytes"] = host_link_bytes
         if atomics:

@@ -21,16 +21,11 @@
 
 #include "gm_cuscan_sig.h"
 #include "gm_probe_common.h"
+#include "gm_where.h"  // Where, where_am_i(): shared with the attributed burn-in
 
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// s_getreg immediate: (size - 1) << 11 | offset << 6 | register
-constexpr int kRegHwId = 4, kRegXccId = 20;
-constexpr int getreg(int size, int offset, int reg) {
-  return ((size - 1) << 11) | (offset << 6) | reg;
-}
 
 struct Slot {
   uint32_t runs, failed_runs, tests_failed, simds_seen, simds_failed;
@@ -68,18 +63,6 @@ __device__ __noinline__ void report(DevTable* tab, uint32_t id, uint32_t simd, u
     r->got = g;
     r->pad = 0;
   }
-}
-
-struct Where {
-  uint32_t id, simd;
-};
-
-__device__ __forceinline__ Where where_am_i() {
-  Where at;
-  at.id = (__builtin_amdgcn_s_getreg(getreg(4, 0, kRegXccId)) << 8) |
-          __builtin_amdgcn_s_getreg(getreg(8, 8, kRegHwId));
-  at.simd = __builtin_amdgcn_s_getreg(getreg(2, 4, kRegHwId));
-  return at;
 }
 
 // What became of one test's signature: the injected flip, then the compare (or the raw store).

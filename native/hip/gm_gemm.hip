@@ -34,6 +34,9 @@ constexpr int kGemmNtDefault = 5;  // profiles/history/r1_gemm: V5 +2.9 % over V
 __device__ __forceinline__ void gemm_tile_of(int M, int N, int& tm, int& tn) {
   gemm_tile_of<g256::TM, g256::TN, g256::kGroupM>(M, N, tm, tn);
 }
+__device__ __forceinline__ void gemm_tile_of(int M, int N, int& tm, int& tn, int r) {
+  gemm_tile_of<g256::TM, g256::TN, g256::kGroupM>(M, N, tm, tn, r);
+}
 
 // V1 — the plain schedule, kept as the reference point for V5: all 24 fragment reads of the
 // 64-deep K-tile are issued up front, so the second k-step's reads overlap the first step's
@@ -135,17 +138,29 @@ __global__ __launch_bounds__(512) void k_gemm_nt256(const __bf16* __restrict__ A
 // tile t+1 are read. Every fragment-read batch then overlaps 32 MFMAs of the same wave, and
 // register use stays at two fragment sets (like V1). The barrier sits mid-tile, so the next
 // tile's DMA is issued right after it.
-__global__ __launch_bounds__(512) void k_gemm_nt256p(const __bf16* __restrict__ A,
-                                                     const __bf16* __restrict__ Bt,
-                                                     __bf16* __restrict__ C, int M, int N,
-                                                     int K) {
+//
+// kTraced: the attributed burn-in's form of the same schedule. The tile comes from the map
+// rotated by tr.r, thread 0 stores the block's CU id under the tile, and a block on the injected
+// CU flips element (0, 0) of its tile on the way out (trace_block, gm_gemm_shared.h). Nothing
+// else differs: operands, order of summation and epilogue are the plain form's.
+template <bool kTraced>
+__device__ __forceinline__ void gemm_nt256p_block(const __bf16* __restrict__ A,
+                                                  const __bf16* __restrict__ Bt,
+                                                  __bf16* __restrict__ C, int M, int N, int K,
+                                                  const GemmTrace& tr) {
   using namespace g256;
   __shared__ __attribute__((aligned(1024))) char lds[kLdsBytes];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   int tm, tn;
-  gemm_tile_of(M, N, tm, tn);
+  uint32_t flip = 0;
+  if constexpr (kTraced) {
+    gemm_tile_of(M, N, tm, tn, tr.r);
+    flip = trace_block(tr, tm * (N / TN) + tn);
+  } else {
+    gemm_tile_of(M, N, tm, tn);
+  }
   const int srow = 8 * wave + (lane >> 3);
   const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
   const __bf16* a_src = A + (size_t)(tm * TM + srow) * K + schunk * 8;
@@ -224,7 +239,23 @@ __global__ __launch_bounds__(512) void k_gemm_nt256p(const __bf16* __restrict__ 
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] = (__bf16)acc[i][j][r];
+        C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] =
+            kTraced && i == 0 && j == 0 && r == 0 ? bf16_flipped(acc[0][0][0], flip)
+                                                  : (__bf16)acc[i][j][r];
+}
+
+__global__ __launch_bounds__(512) void k_gemm_nt256p(const __bf16* __restrict__ A,
+                                                     const __bf16* __restrict__ Bt,
+                                                     __bf16* __restrict__ C, int M, int N,
+                                                     int K) {
+  gemm_nt256p_block<false>(A, Bt, C, M, N, K, GemmTrace{});
+}
+
+__global__ __launch_bounds__(512) void k_gemm_nt256p_traced(const __bf16* __restrict__ A,
+                                                            const __bf16* __restrict__ Bt,
+                                                            __bf16* __restrict__ C, int M, int N,
+                                                            int K, GemmTrace tr) {
+  gemm_nt256p_block<true>(A, Bt, C, M, N, K, tr);
 }
 
 // Deterministic uniform [-1, 1] bf16 fill (random operands: zero-filled ones overstate a GEMM).
@@ -355,6 +386,93 @@ int gm_probe_burn_in_flip(int dev, int n, double seconds, int n_flips,
       n, seconds, n_flips, flip_elems, flip_masks,
       [&](void* c) { return gm_probe_gemm_nt(da.p, db.p, c, n, n, n, nullptr); }, tflops,
       mismatches, iters);
+}
+
+// ------------------------------------------------------------------ attributed burn-in
+
+int gm_probe_burn_in_blame(const gm_burnin_event_t* events, int64_t n_events,
+                           const uint8_t* exonerated, int tiles, gm_burnin_attr_t* out,
+                           gm_burnin_blamed_t* blamed, int blamed_cap) {
+  if (!out || tiles <= 0 || !exonerated || n_events < 0 || (n_events > 0 && !events) ||
+      blamed_cap < 0 || (blamed_cap > 0 && !blamed))
+    return (int)hipErrorInvalidValue;
+  *out = gm_burnin_attr_t{};
+  const GmBurninBlame b = gm_burnin_blame(events, n_events, exonerated, tiles);
+  if (b.bad_event) return (int)hipErrorInvalidValue;
+  gm_burnin_store_blame(b, events, out, blamed, blamed_cap);
+  return 0;
+}
+
+int gm_probe_burn_in_tile_map(int M, int N, int block, int r, int* tm, int* tn, int* step) {
+  using namespace g256;
+  if (!tm || !tn || !step || M <= 0 || N <= 0 || M % TM || N % TN)
+    return (int)hipErrorInvalidValue;
+  const int64_t grid = (int64_t)(M / TM) * (N / TN);
+  if (grid > INT32_MAX || block < 0 || block >= grid || r < 0 || r >= grid)
+    return (int)hipErrorInvalidValue;
+  gm_gemm_tile_map<TM, TN, kGroupM>(block, (int)grid, M, N, r, *tm, *tn);
+  *step = gm_burnin_step((int)grid);
+  return 0;
+}
+
+int gm_probe_gemm_nt_traced(const void* A, const void* Bt, void* C, int M, int N, int K, int r,
+                            uint32_t* cu_of_tile, const gm_burnin_inject_t* inject,
+                            void* stream) {
+  using namespace g256;
+  if (M <= 0 || N <= 0 || K <= 0 || M % TM || N % TN || K % TK || !A || !Bt || !C)
+    return (int)hipErrorInvalidValue;
+  const int grid = (M / TM) * (N / TN);
+  if (r < 0 || r >= grid || !cu_of_tile || ((uintptr_t)cu_of_tile & 3) ||
+      !burn_in_inject_ok(inject) || (inject && inject->first))
+    return (int)hipErrorInvalidValue;
+  const GemmTrace tr{r, cu_of_tile, nullptr, inject ? inject->id : 0,
+                     inject ? inject->mask : 0};
+  hipLaunchKernelGGL(k_gemm_nt256p_traced, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const __bf16*)A, (const __bf16*)Bt, (__bf16*)C, M, N, K, tr);
+  return (int)hipGetLastError();
+}
+
+int gm_probe_gemm_nt_traced_info(int* num_regs, int* scratch_bytes) {
+  if (!num_regs || !scratch_bytes) return (int)hipErrorInvalidValue;
+  hipFuncAttributes attr;
+  GM_CHECK(hipFuncGetAttributes(&attr, (const void*)k_gemm_nt256p_traced));
+  *num_regs = attr.numRegs;
+  *scratch_bytes = (int)attr.localSizeBytes;
+  return 0;
+}
+
+int gm_probe_burn_in_attr(int dev, int n, double seconds, int n_flips,
+                          const uint64_t* flip_elems, const uint16_t* flip_masks,
+                          const gm_burnin_inject_t* inject, double* tflops,
+                          uint64_t* mismatches, int* iters, gm_burnin_attr_t* attr,
+                          gm_burnin_blamed_t* blamed, int blamed_cap) {
+  using namespace g256;
+  *tflops = 0;
+  *mismatches = 0;
+  *iters = 0;
+  if (!attr || blamed_cap < 0 || (blamed_cap > 0 && !blamed)) return (int)hipErrorInvalidValue;
+  *attr = gm_burnin_attr_t{};
+  if (n <= 0 || n % TM || seconds <= 0 || !burn_in_inject_ok(inject))
+    return (int)hipErrorInvalidValue;
+  const size_t elems = (size_t)n * n;
+  if (!burn_in_flips_ok(elems, n_flips, flip_elems, flip_masks)) return (int)hipErrorInvalidValue;
+  DeviceGuard g(dev);
+  if (!g.ok) return (int)hipErrorInvalidDevice;
+  DevBuf da, db;
+  GM_CHECK(da.alloc(elems * 2));
+  GM_CHECK(db.alloc(elems * 2));
+  int e = launch_fill_bf16(da.p, elems, 0x5151u, nullptr);
+  if (!e) e = launch_fill_bf16(db.p, elems, 0xa3a3u, nullptr);
+  if (e) return e;
+  return burn_in_attr_loop(
+      n, seconds, n_flips, flip_elems, flip_masks, inject,
+      [&](void* c, const GemmTrace& tr) {
+        hipLaunchKernelGGL(k_gemm_nt256p_traced, dim3((n / TM) * (n / TN)), dim3(kThreads), 0,
+                           nullptr, (const __bf16*)da.p, (const __bf16*)db.p, (__bf16*)c, n, n, n,
+                           tr);
+        return (int)hipGetLastError();
+      },
+      tflops, mismatches, iters, attr, blamed, blamed_cap);
 }
 
 }  // extern "C"

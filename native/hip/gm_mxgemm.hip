@@ -57,12 +57,16 @@ __device__ __forceinline__ i32x8 mx_fragment(const char* sb, int off, int kk) {
   }
 }
 
-template <int FMT>
-__global__ __launch_bounds__(512) void k_mxgemm_nt(const uint8_t* __restrict__ A,
-                                                   const uint8_t* __restrict__ sA,
-                                                   const uint8_t* __restrict__ Bt,
-                                                   const uint8_t* __restrict__ sB,
-                                                   __bf16* __restrict__ C, int M, int N, int K) {
+// kTraced: the attributed burn-in's form, as in gm_gemm.hip: the tile from the map rotated by
+// tr.r, the block's CU id stored under it, element (0, 0) flipped on the injected CU; operands,
+// order of summation and epilogue are the plain form's.
+template <int FMT, bool kTraced>
+__device__ __forceinline__ void mxgemm_nt_block(const uint8_t* __restrict__ A,
+                                                const uint8_t* __restrict__ sA,
+                                                const uint8_t* __restrict__ Bt,
+                                                const uint8_t* __restrict__ sB,
+                                                __bf16* __restrict__ C, int M, int N, int K,
+                                                const GemmTrace& tr) {
   using namespace mx256;
   constexpr int kSteps = FMT == GM_MX_FP4 ? 2 : 1;  // MFMAs of K = 128 per accumulator and K-tile
   __shared__ __attribute__((aligned(1024))) char lds[kLdsBytes];
@@ -70,7 +74,13 @@ __global__ __launch_bounds__(512) void k_mxgemm_nt(const uint8_t* __restrict__ A
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   int tm, tn;
-  gemm_tile_of<TM, TN, kGroupM>(M, N, tm, tn);
+  uint32_t flip = 0;
+  if constexpr (kTraced) {
+    gemm_tile_of<TM, TN, kGroupM>(M, N, tm, tn, tr.r);
+    flip = trace_block(tr, tm * (N / TN) + tn);
+  } else {
+    gemm_tile_of<TM, TN, kGroupM>(M, N, tm, tn);
+  }
 
   // Operand staging, as in k_gemm_nt256: wave w moves 1 KiB chunks c = w + 8i of each operand's
   // 256-row tile; lane l writes row 8c + (l>>3), slot l&7 = logical chunk (l&7) ^ ((row>>1)&7).
@@ -157,7 +167,28 @@ __global__ __launch_bounds__(512) void k_mxgemm_nt(const uint8_t* __restrict__ A
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] = (__bf16)acc[i][j][r];
+        C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] =
+            kTraced && i == 0 && j == 0 && r == 0 ? bf16_flipped(acc[0][0][0], flip)
+                                                  : (__bf16)acc[i][j][r];
+}
+
+template <int FMT>
+__global__ __launch_bounds__(512) void k_mxgemm_nt(const uint8_t* __restrict__ A,
+                                                   const uint8_t* __restrict__ sA,
+                                                   const uint8_t* __restrict__ Bt,
+                                                   const uint8_t* __restrict__ sB,
+                                                   __bf16* __restrict__ C, int M, int N, int K) {
+  mxgemm_nt_block<FMT, false>(A, sA, Bt, sB, C, M, N, K, GemmTrace{});
+}
+
+template <int FMT>
+__global__ __launch_bounds__(512) void k_mxgemm_nt_traced(const uint8_t* __restrict__ A,
+                                                          const uint8_t* __restrict__ sA,
+                                                          const uint8_t* __restrict__ Bt,
+                                                          const uint8_t* __restrict__ sB,
+                                                          __bf16* __restrict__ C, int M, int N,
+                                                          int K, GemmTrace tr) {
+  mxgemm_nt_block<FMT, true>(A, sA, Bt, sB, C, M, N, K, tr);
 }
 
 // The packed element bytes of an operand, then its scale bytes: one grid-stride loop each.
@@ -171,6 +202,22 @@ __global__ __launch_bounds__(256) void k_mx_fill(int fmt, int cls, uint32_t seed
   for (size_t i = first; i < scale_bytes; i += stride)
     scales[i] = (uint8_t)gm_mx_scale(cls, seed, (uint32_t)(i / kblocks), (uint32_t)(i % kblocks),
                                      kblocks);
+}
+
+// The one launch of the traced kernels; the arguments were checked.
+int launch_mxgemm_traced(int fmt, const void* A, const void* sA, const void* Bt, const void* sB,
+                         void* C, int M, int N, int K, const GemmTrace& tr, hipStream_t stream) {
+  using namespace mx256;
+  const dim3 grid((M / TM) * (N / TN)), block(kThreads);
+  if (fmt == GM_MX_FP4)
+    hipLaunchKernelGGL(k_mxgemm_nt_traced<GM_MX_FP4>, grid, block, 0, stream, (const uint8_t*)A,
+                       (const uint8_t*)sA, (const uint8_t*)Bt, (const uint8_t*)sB, (__bf16*)C, M,
+                       N, K, tr);
+  else
+    hipLaunchKernelGGL(k_mxgemm_nt_traced<GM_MX_FP8>, grid, block, 0, stream, (const uint8_t*)A,
+                       (const uint8_t*)sA, (const uint8_t*)Bt, (const uint8_t*)sB, (__bf16*)C, M,
+                       N, K, tr);
+  return (int)hipGetLastError();
 }
 
 bool shape_ok(int fmt, int M, int N, int K) {
@@ -255,6 +302,69 @@ int gm_probe_mx_burn_in_flip(int dev, int fmt, int n, double seconds, int n_flip
       n, seconds, n_flips, flip_elems, flip_masks,
       [&](void* c) { return gm_probe_mxgemm_nt(fmt, da.p, dsa.p, db.p, dsb.p, c, n, n, n, nullptr); },
       tflops, mismatches, iters);
+}
+
+// ------------------------------------------------------------------ attributed burn-in
+
+int gm_probe_mxgemm_nt_traced(int fmt, const void* A, const void* sA, const void* Bt,
+                              const void* sB, void* C, int M, int N, int K, int r,
+                              uint32_t* cu_of_tile, const gm_burnin_inject_t* inject,
+                              void* stream) {
+  using namespace mx256;
+  if (!shape_ok(fmt, M, N, K) || !A || !sA || !Bt || !sB || !C || ((uintptr_t)A & 15) ||
+      ((uintptr_t)Bt & 15) || ((uintptr_t)sA & 3) || ((uintptr_t)sB & 3) || ((uintptr_t)C & 1))
+    return (int)hipErrorInvalidValue;
+  if (r < 0 || r >= (M / TM) * (N / TN) || !cu_of_tile || ((uintptr_t)cu_of_tile & 3) ||
+      !burn_in_inject_ok(inject) || (inject && inject->first))
+    return (int)hipErrorInvalidValue;
+  return launch_mxgemm_traced(
+      fmt, A, sA, Bt, sB, C, M, N, K,
+      GemmTrace{r, cu_of_tile, nullptr, inject ? inject->id : 0, inject ? inject->mask : 0},
+      (hipStream_t)stream);
+}
+
+int gm_probe_mxgemm_nt_traced_info(int fmt, int* num_regs, int* scratch_bytes) {
+  if (!gm_mx_format_ok(fmt) || !num_regs || !scratch_bytes) return (int)hipErrorInvalidValue;
+  hipFuncAttributes attr;
+  GM_CHECK(hipFuncGetAttributes(&attr, fmt == GM_MX_FP4
+                                           ? (const void*)k_mxgemm_nt_traced<GM_MX_FP4>
+                                           : (const void*)k_mxgemm_nt_traced<GM_MX_FP8>));
+  *num_regs = attr.numRegs;
+  *scratch_bytes = (int)attr.localSizeBytes;
+  return 0;
+}
+
+int gm_probe_mx_burn_in_attr(int dev, int fmt, int n, double seconds, int n_flips,
+                             const uint64_t* flip_elems, const uint16_t* flip_masks,
+                             const gm_burnin_inject_t* inject, double* tflops,
+                             uint64_t* mismatches, int* iters, gm_burnin_attr_t* attr,
+                             gm_burnin_blamed_t* blamed, int blamed_cap) {
+  *tflops = 0;
+  *mismatches = 0;
+  *iters = 0;
+  if (!attr || blamed_cap < 0 || (blamed_cap > 0 && !blamed)) return (int)hipErrorInvalidValue;
+  *attr = gm_burnin_attr_t{};
+  if (!shape_ok(fmt, n, n, n) || seconds <= 0 || !burn_in_inject_ok(inject))
+    return (int)hipErrorInvalidValue;
+  if (!burn_in_flips_ok((size_t)n * n, n_flips, flip_elems, flip_masks))
+    return (int)hipErrorInvalidValue;
+  DeviceGuard g(dev);
+  if (!g.ok) return (int)hipErrorInvalidDevice;
+  const size_t eb = (size_t)n * gm_mx_row_bytes(fmt, (size_t)n), sb = (size_t)n * n / GM_MX_BLOCK;
+  DevBuf da, db, dsa, dsb;
+  GM_CHECK(da.alloc(eb));
+  GM_CHECK(db.alloc(eb));
+  GM_CHECK(dsa.alloc(sb));
+  GM_CHECK(dsb.alloc(sb));
+  int e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0x5151u, n, n, da.p, dsa.p, nullptr);
+  if (!e) e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0xa3a3u, n, n, db.p, dsb.p, nullptr);
+  if (e) return e;
+  return burn_in_attr_loop(
+      n, seconds, n_flips, flip_elems, flip_masks, inject,
+      [&](void* c, const GemmTrace& tr) {
+        return launch_mxgemm_traced(fmt, da.p, dsa.p, db.p, dsb.p, c, n, n, n, tr, nullptr);
+      },
+      tflops, mismatches, iters, attr, blamed, blamed_cap);
 }
 
 }  // extern "C"

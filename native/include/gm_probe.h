@@ -481,6 +481,137 @@ int gm_probe_mx_burn_in_flip(int dev, int fmt, int n, double seconds, int n_flip
                              const uint64_t* flip_elems, const uint16_t* flip_masks,
                              double* tflops, uint64_t* mismatches, int* iters);
 
+// ------------------------------------------------------------------ attributed burn-in
+// The burn-ins above compare the GPU with itself through a fixed block → tile map, so a tile is
+// recomputed where the reference computed it, and a mismatch names no unit. The attributed
+// burn-in is the same load with the map rotated from one iteration to the next: a tile's bits
+// depend on its operands and the kernel's summation order, not on the block that computes it,
+// so block b may compute the tile the plain map gives block (b + r) mod grid, for any r. Every
+// block stores the 12-bit id of the CU it ran on (the scans' id: XCC_ID << 8 | HW_ID[15:8]) under
+// its tile, and a per-tile compare turns a mismatch into an event between two known CUs. The
+// code shared by host and device (the map, the step, the blame rule) is gm_burnin_attr.h.
+//
+// The loop, on the null stream, in order:
+//   warm-up    one whole iteration outside the timing: a traced GEMM at r = 0 without the
+//              injection, and the compare of its result with itself; `first` = the CU of its
+//              tile 0, which the later kernels read on the device
+//   reference  one traced GEMM at r = 0 into the reference and the same compare; its CU map is
+//              kept; the flips are applied to it exactly as gm_probe_burn_in_flip applies them
+//              From the warm-up on the stream holds GEMM, compare, GEMM, compare ... with no
+//              host round trip in between (the flips' copies apart). On the one MI355X this was
+//              measured on, where the blocks of a launch run depends on the launches before it
+//              and repeats with a short period, so a warm-up that is one more turn of the
+//              loop's own sequence makes `first` a CU the loop comes back to. That is observed,
+//              not promised.
+//   iteration i = 1, 2, ...  a traced GEMM at r = (i · step) mod grid, then the per-tile compare.
+//              grid = (n / 256)² blocks = tiles; step is coprime to grid and, where grid > 8, no
+//              multiple of 8 (gm_burnin_step), so a tile changes XCD from one iteration to the
+//              next and meets every block within grid iterations.
+// The compare (one block per tile) counts the tile's differing 16-byte words, the unit and the
+// total of the plain burn-in's compare. A tile with none whose CU differs from the reference's is
+// marked exonerated: another CU reproduced the reference's bits. A tile with some adds them to
+// *mismatches and appends an event to a log of GM_BURNIN_LOG_CAP entries; later events are
+// counted (events) but not logged (log_overflow).
+//
+// The blame, decided on the host after the loop (exoneration may come after the event): an
+// event at tile t with worker W and reference R blames W if t is exonerated or W == R, else R.
+// A tile no other CU ever reproduced makes the reference the odd one out. Under log_overflow
+// only the logged events are blamed.
+//
+// The injection is the negative control that the flips cannot be: a CU that is consistently
+// wrong, in the reference too. Every block that finds itself on CU `id` XORs `mask` into the
+// bf16 element (0, 0) of its tile on the way out. first != 0: the id is taken from the warm-up
+// (the CU that computed tile 0) and `id` is ignored.
+#define GM_BURNIN_LOG_CAP 1024
+#define GM_BURNIN_MAX_RECORDS 16
+
+typedef struct gm_burnin_event {
+  uint32_t iteration;  // 1-based
+  uint32_t tile;       // row-major over the (n / 256)² tiles
+  uint32_t worker;     // CU id of the block that computed the mismatching tile
+  uint32_t reference;  // CU id of the block that computed the reference's tile
+  uint32_t words;      // differing 16-byte words of the tile
+} gm_burnin_event_t;
+
+typedef struct gm_burnin_inject {
+  uint32_t id;     // < GM_CUSCAN_IDS
+  uint32_t mask;   // 1..0xFFFF
+  uint32_t first;  // nonzero: the CU of the warm-up's tile 0 instead of id
+} gm_burnin_inject_t;
+
+typedef struct gm_burnin_blamed {
+  uint32_t id;
+  uint32_t events;        // = as_worker + as_reference
+  uint32_t as_worker;     // events in which it was blamed as the worker
+  uint32_t as_reference;  // ... as the reference
+  uint64_t words;
+} gm_burnin_blamed_t;
+
+typedef struct gm_burnin_attr {
+  uint32_t tiles, grid, step;
+  uint32_t rotations;         // distinct r among the iterations
+  uint32_t cus_seen;          // distinct CU ids over the warm-up's, the reference's and every
+                              // iteration's map
+  uint32_t tiles_moved;       // tiles some iteration computed on another CU than the reference
+  uint32_t tiles_exonerated;
+  uint32_t logged;            // min(events, GM_BURNIN_LOG_CAP)
+  uint32_t log_overflow;      // events > logged
+  uint32_t first_id;          // the CU of the warm-up's tile 0
+  uint32_t inject_id;         // the id injected into; GM_CUSCAN_ANY without an injection
+  uint32_t n_blamed;          // units blamed; the first min(n_blamed, blamed_cap) are stored
+  uint32_t records_filled;    // min(logged, GM_BURNIN_MAX_RECORDS)
+  uint64_t events;            // mismatching (iteration, tile) pairs
+  gm_burnin_event_t records[GM_BURNIN_MAX_RECORDS];  // the first logged events, in log order
+} gm_burnin_attr_t;
+
+// Host only, no GPU: the blame rule over a log. Reads the first min(n_events,
+// GM_BURNIN_LOG_CAP) of `events` (the rest were counted, not logged) and exonerated[0..tiles);
+// stores the blamed units, most events first (ties: lower id first), and the summary fields
+// events, logged, log_overflow, tiles_exonerated, n_blamed and records of *out (the others
+// zero). An
+// event whose tile is >= tiles or whose ids are >= GM_CUSCAN_IDS, tiles <= 0, n_events < 0,
+// blamed_cap < 0 or a missing array: hipErrorInvalidValue.
+int gm_probe_burn_in_blame(const gm_burnin_event_t* events, int64_t n_events,
+                           const uint8_t* exonerated, int tiles, gm_burnin_attr_t* out,
+                           gm_burnin_blamed_t* blamed, int blamed_cap);
+// Host only: block `block` of a grid of (M / 256) · (N / 256) blocks computes tile
+// (*tm, *tn) at rotation r, the map the traced kernels evaluate on the device; r = 0 is the
+// plain kernels' map. *step = gm_burnin_step(grid). M, N multiples of 256, 0 <= block < grid,
+// 0 <= r < grid, else hipErrorInvalidValue.
+int gm_probe_burn_in_tile_map(int M, int N, int block, int r, int* tm, int* tn, int* step);
+// One traced GEMM on caller-owned device buffers: gm_probe_gemm_nt's and gm_probe_mxgemm_nt's
+// arguments and checks, then the rotation r, 0 <= r < grid, where each block stores its CU id
+// (cu_of_tile[tile], a device pointer, 4-byte aligned, grid entries) and the injection, which
+// may be NULL and whose `first` must be 0. Bad arguments: hipErrorInvalidValue before any HIP
+// call. Asynchronous on `stream`.
+int gm_probe_gemm_nt_traced(const void* A, const void* Bt, void* C, int M, int N, int K, int r,
+                            uint32_t* cu_of_tile, const gm_burnin_inject_t* inject,
+                            void* stream);
+int gm_probe_mxgemm_nt_traced(int fmt, const void* A, const void* sA, const void* Bt,
+                              const void* sB, void* C, int M, int N, int K, int r,
+                              uint32_t* cu_of_tile, const gm_burnin_inject_t* inject,
+                              void* stream);
+// Registers and scratch bytes of the traced kernels: the accumulators must stay in registers
+// there too, so scratch must be 0.
+int gm_probe_gemm_nt_traced_info(int* num_regs, int* scratch_bytes);
+int gm_probe_mxgemm_nt_traced_info(int fmt, int* num_regs, int* scratch_bytes);
+// The attributed bf16 burn-in: gm_probe_burn_in_flip's arguments, operands and meanings of
+// *tflops, *mismatches and *iters, through the loop above. `inject` may be NULL. *attr and the
+// first min(attr->n_blamed, blamed_cap) entries of `blamed` are filled. Bad flips, an injection
+// id >= GM_CUSCAN_IDS (first == 0), a mask of 0 or above 0xFFFF, a missing attr, blamed_cap < 0
+// or blamed_cap > 0 without `blamed`: hipErrorInvalidValue before any HIP call.
+int gm_probe_burn_in_attr(int dev, int n, double seconds, int n_flips,
+                          const uint64_t* flip_elems, const uint16_t* flip_masks,
+                          const gm_burnin_inject_t* inject, double* tflops,
+                          uint64_t* mismatches, int* iters, gm_burnin_attr_t* attr,
+                          gm_burnin_blamed_t* blamed, int blamed_cap);
+// The same for the MX burn-in (gm_probe_mx_burn_in_flip's format, operands and shapes).
+int gm_probe_mx_burn_in_attr(int dev, int fmt, int n, double seconds, int n_flips,
+                             const uint64_t* flip_elems, const uint16_t* flip_masks,
+                             const gm_burnin_inject_t* inject, double* tflops,
+                             uint64_t* mismatches, int* iters, gm_burnin_attr_t* attr,
+                             gm_burnin_blamed_t* blamed, int blamed_cap);
+
 // ------------------------------------------------------------------ lane scan
 // The CU scan's frame again (one 256-thread block per CU, so one wave per SIMD; the whole LDS
 // declared; the CU id read from the registers; a host-computed table compared bit for bit) around
