@@ -289,6 +289,11 @@ class BurninEvent(C.Structure):       # gm_burnin_event_t
                 ("reference", C.c_uint32), ("words", C.c_uint32)]
 
 
+class BurninState(C.Structure):       # gm_burnin_state_t
+    _fields_ = [("total", C.c_uint64), ("cursor", C.c_uint32), ("pad", C.c_uint32),
+                ("log", BurninEvent * BURNIN_LOG_CAP)]
+
+
 class BurninInject(C.Structure):      # gm_burnin_inject_t
     _fields_ = [("id", C.c_uint32), ("mask", C.c_uint32), ("first", C.c_uint32)]
 
@@ -492,6 +497,10 @@ def probe() -> C.CDLL:
         lib.gm_probe_mxgemm_nt_traced.argtypes = lib.gm_probe_mxgemm_nt.argtypes[:-1] + traced
         lib.gm_probe_gemm_nt_traced_info.argtypes = [C.POINTER(C.c_int)] * 2
         lib.gm_probe_mxgemm_nt_traced_info.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 2
+        lib.gm_probe_count_diff_tiles.argtypes = ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_uint32] + [C.c_void_p] * 5)
+        lib.gm_probe_burn_in_state_bytes.argtypes = []
+        lib.gm_probe_burn_in_state_bytes.restype = C.c_uint64
         lib.gm_probe_burn_in_attr.argtypes = (
             lib.gm_probe_burn_in_flip.argtypes[:6] + [C.POINTER(BurninInject)] +
             lib.gm_probe_burn_in_flip.argtypes[6:] +

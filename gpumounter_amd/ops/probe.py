@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import asdict, dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 from gpumounter_amd import _native
 
@@ -523,6 +523,103 @@ def count_diff(a, b, stream=None) -> int:
                                                    _stream_of(a, stream), C.byref(n)),
                "count_diff")
     return n.value
+
+
+BURN_IN_STATE_BYTES = C.sizeof(_native.BurninState)   # gm_probe_burn_in_state_bytes()
+
+
+class CompareState(NamedTuple):
+    """What :func:`count_diff_tiles` accumulates over its calls, device tensors: ``state`` is
+    :data:`BURN_IN_STATE_BYTES` bytes (a ``gm_burnin_state_t``: total, cursor, the log),
+    ``exonerated`` and ``moved`` one int32 per tile, ``seen`` one per CU id. Zeroed by whoever
+    makes it."""
+    state: object
+    exonerated: object
+    moved: object
+    seen: object
+
+
+def count_diff_tiles(a, b, cu, ref_cu, iteration: int, state: Optional[CompareState] = None,
+                     read: bool = True, stream=None):
+    """One per-tile compare of the attributed burn-in (gm_probe_count_diff_tiles, the launch the
+    burn-in's loop uses) of two n × n bf16 device tensors, ``b`` the reference, n a multiple of
+    256; ``cu`` and ``ref_cu`` are the CU maps of the two, int32 tensors with one id per tile
+    (-1, i.e. 0xFFFFFFFF: none stored). Without a ``state`` a zeroed one is made; handing back
+    the returned one accumulates as the iterations of a run do. Waits for the launch and
+    returns ``{"total", "cursor", "events": [(iteration, tile, worker, reference, words), ...]
+    in log order, "exonerated", "moved", "seen": lists of 0 / 1, "state"}``; with
+    ``read=False`` it only launches (asynchronous) and returns ``{"state"}``."""
+    import torch
+
+    for t, what in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16 or t.dim() != 2:
+            raise ProbeError(f"count_diff_tiles: {what} must be a 2-D bf16 torch tensor")
+        if not t.is_contiguous():
+            raise ProbeError(f"count_diff_tiles: {what} must be contiguous")
+    n = int(a.shape[0])
+    if a.shape != (n, n) or b.shape != (n, n) or n == 0 or n % BURN_IN_TILE:
+        raise ProbeError(f"count_diff_tiles: a{tuple(a.shape)} and b{tuple(b.shape)} are not two "
+                         f"n × n results with n a positive multiple of {BURN_IN_TILE}")
+    tiles = (n // BURN_IN_TILE) ** 2
+    if not isinstance(iteration, int) or isinstance(iteration, bool) or \
+            not 0 <= iteration < 1 << 32:
+        raise ProbeError(f"count_diff_tiles: iteration {iteration!r} is not a 32-bit integer")
+
+    def words(t, what: str, count: int) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise ProbeError(f"count_diff_tiles: {what} must be a contiguous int32 torch tensor")
+        if t.numel() != count:
+            raise ProbeError(f"count_diff_tiles: {what} has {t.numel()} entries, not {count}")
+
+    words(cu, "cu", tiles)
+    words(ref_cu, "ref_cu", tiles)
+    if state is None:
+        if a.device.type != "cuda":
+            raise ProbeError(f"count_diff_tiles expects tensors on a HIP device, got {a.device}")
+        state = CompareState(
+            torch.zeros(BURN_IN_STATE_BYTES, dtype=torch.uint8, device=a.device),
+            *(torch.zeros(k, dtype=torch.int32, device=a.device)
+              for k in (tiles, tiles, _native.CUSCAN_IDS)))
+    elif not isinstance(state, CompareState):
+        raise ProbeError("count_diff_tiles: state must be a CompareState")
+    st = state.state
+    if not isinstance(st, torch.Tensor) or not st.is_contiguous() or \
+            st.numel() * st.element_size() != BURN_IN_STATE_BYTES:
+        raise ProbeError(f"count_diff_tiles: the state must be a contiguous tensor of exactly "
+                         f"{BURN_IN_STATE_BYTES} bytes")
+    words(state.exonerated, "exonerated", tiles)
+    words(state.moved, "moved", tiles)
+    words(state.seen, "seen", _native.CUSCAN_IDS)
+    every = (a, b, cu, ref_cu) + tuple(state)
+    if a.device.type != "cuda" or any(t.device != a.device for t in every):
+        raise ProbeError(f"count_diff_tiles expects every tensor on one HIP device, got "
+                         f"{sorted({str(t.device) for t in every})}")
+    if a.data_ptr() % 16 or b.data_ptr() % 16 or st.data_ptr() % 8:
+        raise ProbeError("count_diff_tiles: a and b must be 16-byte and the state 8-byte aligned")
+    s = stream if stream is not None else torch.cuda.current_stream(a.device)
+    with torch.cuda.device(a.device):
+        _check(_native.probe().gm_probe_count_diff_tiles(
+            a.data_ptr(), b.data_ptr(), n, cu.data_ptr(), ref_cu.data_ptr(), iteration,
+            st.data_ptr(), state.exonerated.data_ptr(), state.moved.data_ptr(),
+            state.seen.data_ptr(), C.c_void_p(s.cuda_stream)), "count_diff_tiles")
+    if not read:
+        return {"state": state}
+    s.synchronize()
+    return {**read_compare_state(state), "state": state}
+
+
+def read_compare_state(state: CompareState) -> Dict:
+    """The host's view of a :class:`CompareState` (copies it back; the caller has waited for
+    the compares): total, cursor, the logged events and the three mark arrays."""
+    import numpy as np
+
+    raw = state.state.cpu().numpy().view(np.uint8).tobytes()
+    st = _native.BurninState.from_buffer_copy(raw)
+    events = [(e.iteration, e.tile, e.worker, e.reference, e.words)
+              for e in st.log[:min(st.cursor, _native.BURNIN_LOG_CAP)]]
+    return {"total": st.total, "cursor": st.cursor, "events": events,
+            "exonerated": state.exonerated.cpu().tolist(), "moved": state.moved.cpu().tolist(),
+            "seen": state.seen.cpu().tolist()}
 
 
 def fill_bf16(t, seed: int, stream=None):

@@ -441,6 +441,23 @@ int gm_probe_gemm_nt_traced_info(int* num_regs, int* scratch_bytes) {
   return 0;
 }
 
+int gm_probe_count_diff_tiles(const void* a, const void* b, int n, const uint32_t* cu,
+                              const uint32_t* ref_cu, uint32_t iteration, void* state,
+                              uint32_t* exonerated, uint32_t* moved, uint32_t* seen,
+                              void* stream) {
+  if (n <= 0 || n % kBurninTile || (int64_t)(n / kBurninTile) * (n / kBurninTile) > INT32_MAX)
+    return (int)hipErrorInvalidValue;
+  if (!a || !b || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || !state || ((uintptr_t)state & 7))
+    return (int)hipErrorInvalidValue;
+  for (const void* p : {(const void*)cu, (const void*)ref_cu, (const void*)exonerated,
+                        (const void*)moved, (const void*)seen})
+    if (!p || ((uintptr_t)p & 3)) return (int)hipErrorInvalidValue;
+  return launch_count_diff_tiles(a, b, n, iteration, AttrMaps{cu, ref_cu, exonerated, moved, seen},
+                                 state, (hipStream_t)stream);
+}
+
+uint64_t gm_probe_burn_in_state_bytes(void) { return sizeof(gm_burnin_state_t); }
+
 int gm_probe_burn_in_attr(int dev, int n, double seconds, int n_flips,
                           const uint64_t* flip_elems, const uint16_t* flip_masks,
                           const gm_burnin_inject_t* inject, double* tflops,

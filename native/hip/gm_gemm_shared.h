@@ -5,6 +5,8 @@
 // translation unit gets its own copy.
 #pragma once
 
+#include <stddef.h>
+
 #include "gm_burnin_attr.h"
 #include "gm_probe_common.h"
 #include "gm_where.h"
@@ -145,12 +147,18 @@ int burn_in_loop(int n, double seconds, int n_flips, const uint64_t* flip_elems,
 // ------------------------------------------------------------------ attributed burn-in
 // (contract: gm_probe.h, "attributed burn-in")
 
-// What the per-tile compare accumulates over a run.
+// What the per-tile compare accumulates over a run: gm_burnin_state_t (gm_probe.h) with the
+// total as the type atomicAdd takes.
 struct AttrState {
   unsigned long long total;  // differing 16-B words, k_count_diff's unit and total
   uint32_t cursor, pad;      // events so far; the first GM_BURNIN_LOG_CAP of them are in log[]
   gm_burnin_event_t log[GM_BURNIN_LOG_CAP];
 };
+static_assert(sizeof(AttrState) == sizeof(gm_burnin_state_t) &&
+                  offsetof(AttrState, total) == offsetof(gm_burnin_state_t, total) &&
+                  offsetof(AttrState, cursor) == offsetof(gm_burnin_state_t, cursor) &&
+                  offsetof(AttrState, log) == offsetof(gm_burnin_state_t, log),
+              "the published layout is the kernel's");
 
 // The per-tile maps of a run, device pointers: tiles entries each, seen GM_CUSCAN_IDS.
 struct AttrMaps {
@@ -161,6 +169,8 @@ struct AttrMaps {
 // One block per 256 × 256 bf16 tile of the n × n results a and b (b the reference): the tile's
 // differing 16-B words, 32 per row. Thread 0 then books the tile. Plain stores of 1 for the three
 // marks (every writer stores the same value); atomics only on the total and the log cursor.
+// An id of GM_CUSCAN_IDS or more in either map (0xFFFFFFFF: the block stored nothing) is no CU:
+// the tile marks nothing in seen, and its event carries the ids as read, for the host to refuse.
 __global__ __launch_bounds__(256) void k_count_diff_tiles(const u32x4* __restrict__ a,
                                                           const u32x4* __restrict__ b, int n,
                                                           uint32_t iteration, AttrMaps maps,
@@ -183,7 +193,7 @@ __global__ __launch_bounds__(256) void k_count_diff_tiles(const u32x4* __restric
   if (threadIdx.x != 0) return;
   const uint32_t words = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
   const uint32_t cu = maps.cu[tile], ref = maps.ref_cu[tile];
-  maps.seen[cu & (GM_CUSCAN_IDS - 1)] = 1;
+  if (cu < GM_CUSCAN_IDS && ref < GM_CUSCAN_IDS) maps.seen[cu] = 1;
   if (cu != ref) maps.moved[tile] = 1;
   if (words == 0) {
     if (cu != ref) maps.exonerated[tile] = 1;  // another CU reproduced the reference's bits
@@ -193,6 +203,16 @@ __global__ __launch_bounds__(256) void k_count_diff_tiles(const u32x4* __restric
   const uint32_t slot = atomicAdd(&st->cursor, 1u);
   if (slot < GM_BURNIN_LOG_CAP)
     st->log[slot] = gm_burnin_event_t{iteration, (uint32_t)tile, cu, ref, words};
+}
+
+// The one launch of the per-tile compare, one block per tile of the n × n results: the traced
+// loop and gm_probe_count_diff_tiles share it.
+inline int launch_count_diff_tiles(const void* a, const void* b, int n, uint32_t iteration,
+                                   const AttrMaps& maps, void* state, hipStream_t s) {
+  const int tiles = (n / kBurninTile) * (n / kBurninTile);
+  hipLaunchKernelGGL(k_count_diff_tiles, dim3(tiles), dim3(256), 0, s, (const u32x4*)a,
+                     (const u32x4*)b, n, iteration, maps, (AttrState*)state);
+  return (int)hipGetLastError();
 }
 
 // The injection of an attributed burn-in, checked: NULL, or an id and a 16-bit mask.
@@ -234,13 +254,12 @@ int burn_in_attr_loop(int n, double seconds, int n_flips, const uint64_t* flip_e
   // it marks nothing but the CUs it saw). It loads both kernels' code and leaves `first`, the CU
   // of its tile 0, in dwarm[0], where the injection reads it on the device. From here on the
   // stream holds GEMM, compare, GEMM, compare ... without a host round trip in between (the
-  // flips' copies apart), the sequence of launches the timed loop continues.
+  // flips' copies apart), the sequence of launches the timed loop continues. The compare goes
+  // through launch_count_diff_tiles, the launch gm_probe_count_diff_tiles is tested through.
   const auto compare = [&](const void* c, const void* cu, const void* ref_cu, uint32_t iteration) {
     const AttrMaps maps{(const uint32_t*)cu, (const uint32_t*)ref_cu, (uint32_t*)dexon.p,
                         (uint32_t*)dmoved.p, (uint32_t*)dseen.p};
-    hipLaunchKernelGGL(k_count_diff_tiles, dim3(tiles), dim3(256), 0, nullptr, (const u32x4*)c,
-                       (const u32x4*)dref.p, n, iteration, maps, (AttrState*)dst.p);
-    return (int)hipGetLastError();
+    return launch_count_diff_tiles(c, dref.p, n, iteration, maps, dst.p, nullptr);
   };
   GemmTrace tr{0, (uint32_t*)dwarm.p, nullptr, 0, 0};
   int e = gemm(dref.p, tr);
@@ -298,10 +317,11 @@ int burn_in_attr_loop(int n, double seconds, int n_flips, const uint64_t* flip_e
   GM_CHECK(hipMemcpy(seen.data(), dseen.p, seen_bytes, hipMemcpyDeviceToHost));
   const AttrState* st = (const AttrState*)raw.data();
   std::vector<uint8_t> exonerated(tiles);
-  for (int t = 0; t < tiles; ++t) {
-    exonerated[t] = exon[t] != 0;
-    attr->tiles_moved += moved[t] != 0;
-  }
+  for (int t = 0; t < tiles; ++t) exonerated[t] = exon[t] != 0;
+  const GmBurninBlame blame = gm_burnin_blame(st->log, st->cursor, exonerated.data(), tiles);
+  // an event between ids that are no CU's (a block stored none) blames nobody: no verdict
+  if (blame.bad_event) return (int)hipErrorUnknown;
+  for (int t = 0; t < tiles; ++t) attr->tiles_moved += moved[t] != 0;
   for (uint32_t id = 0; id < GM_CUSCAN_IDS; ++id) attr->cus_seen += seen[id] != 0;
   attr->tiles = (uint32_t)tiles;
   attr->grid = (uint32_t)grid;
@@ -309,8 +329,7 @@ int burn_in_attr_loop(int n, double seconds, int n_flips, const uint64_t* flip_e
   attr->rotations = (uint32_t)(done < grid ? done : grid);  // step is coprime to the grid
   attr->first_id = first;
   attr->inject_id = !inject ? GM_CUSCAN_ANY : inject->first ? first : inject->id;
-  gm_burnin_store_blame(gm_burnin_blame(st->log, st->cursor, exonerated.data(), tiles), st->log,
-                        attr, blamed, blamed_cap);
+  gm_burnin_store_blame(blame, st->log, attr, blamed, blamed_cap);
   *iters = done;
   *mismatches = st->total;
   if (ms > 0) *tflops = 2.0 * n * (double)n * n * done / (ms * 1e-3) / 1e12;

@@ -74,7 +74,11 @@ struct GmBurninBlame {
 // The blame rule. An event at tile t with worker W and reference R blames W if t is exonerated
 // (another CU reproduced the reference's bits there, so the reference stands) or W == R (one
 // unit disagreeing with itself), else R: no other CU ever reproduced the reference's tile, so
-// the reference is the odd one out, whether its fault was transient or consistent. Only the
+// the reference is the odd one out, whether its fault was transient or consistent. The role
+// follows the same reasoning: W is blamed as the worker, R as the reference, and a unit that
+// disagrees with itself (W == R) as the worker unless t is not exonerated and another unit
+// disagreed with that reference in a logged event too. Then the reference is the odd one out
+// for its own CU as for every other, and the event counts as_reference. Only the
 // first min(n_events, GM_BURNIN_LOG_CAP) events exist; the others were counted, not logged.
 inline GmBurninBlame gm_burnin_blame(const gm_burnin_event_t* events, int64_t n_events,
                                      const uint8_t* exonerated, int tiles) {
@@ -83,14 +87,21 @@ inline GmBurninBlame gm_burnin_blame(const gm_burnin_event_t* events, int64_t n_
   out.logged = (uint32_t)std::min<int64_t>(n_events, GM_BURNIN_LOG_CAP);
   out.log_overflow = out.events > out.logged;
   for (int t = 0; t < tiles; ++t) out.tiles_exonerated += exonerated[t] != 0;
+  const auto bad = [&](const gm_burnin_event_t& e) {
+    return e.tile >= (uint32_t)tiles || e.worker >= GM_CUSCAN_IDS || e.reference >= GM_CUSCAN_IDS;
+  };
+  std::vector<uint8_t> others(tiles > 0 ? tiles : 0, 0);  // another unit disagreed with the tile
+  for (uint32_t i = 0; i < out.logged; ++i)
+    if (!bad(events[i]) && events[i].worker != events[i].reference) others[events[i].tile] = 1;
   std::vector<int> slot(GM_CUSCAN_IDS, -1);
   for (uint32_t i = 0; i < out.logged; ++i) {
     const gm_burnin_event_t& e = events[i];
-    if (e.tile >= (uint32_t)tiles || e.worker >= GM_CUSCAN_IDS || e.reference >= GM_CUSCAN_IDS) {
+    if (bad(e)) {
       out.bad_event = true;
       continue;
     }
-    const bool worker = exonerated[e.tile] != 0 || e.worker == e.reference;
+    const bool worker =
+        exonerated[e.tile] != 0 || (e.worker == e.reference && others[e.tile] == 0);
     const uint32_t id = worker ? e.worker : e.reference;
     if (slot[id] < 0) {
       slot[id] = (int)out.blamed.size();

@@ -511,12 +511,22 @@ int gm_probe_mx_burn_in_flip(int dev, int fmt, int n, double seconds, int n_flip
 // total of the plain burn-in's compare. A tile with none whose CU differs from the reference's is
 // marked exonerated: another CU reproduced the reference's bits. A tile with some adds them to
 // *mismatches and appends an event to a log of GM_BURNIN_LOG_CAP entries; later events are
-// counted (events) but not logged (log_overflow).
+// counted (events) but not logged (log_overflow). Every tile also marks its CU in `seen` and,
+// where its CU differs from the reference's, itself in `moved`. An id of GM_CUSCAN_IDS or more
+// in either map is no CU's (0xFFFFFFFF: the block stored nothing): such a tile marks nothing
+// in `seen`, and its event is logged with the ids as read.
 //
 // The blame, decided on the host after the loop (exoneration may come after the event): an
 // event at tile t with worker W and reference R blames W if t is exonerated or W == R, else R.
-// A tile no other CU ever reproduced makes the reference the odd one out. Under log_overflow
-// only the logged events are blamed.
+// A tile no other CU ever reproduced makes the reference the odd one out. W is blamed in the
+// role of the worker, R in the role of the reference. W == R (in a grid of g blocks every g-th
+// iteration runs at r = 0, where a block may land on the reference's CU again) counts as the
+// worker's, except at a tile that is not exonerated and at which another CU disagreed with the
+// reference in a logged event too: the reference is then the odd one out for its own CU as for
+// the others, and the event counts as the reference's. Under log_overflow
+// only the logged events are blamed. A logged event with an id that is no CU's blames nobody,
+// so a run that holds one gives no verdict: the burn-in returns hipErrorUnknown, as it does when
+// the warm-up's tile 0 stored no id.
 //
 // The injection is the negative control that the flips cannot be: a CU that is consistently
 // wrong, in the reference too. Every block that finds itself on CU `id` XORs `mask` into the
@@ -532,6 +542,15 @@ typedef struct gm_burnin_event {
   uint32_t reference;  // CU id of the block that computed the reference's tile
   uint32_t words;      // differing 16-byte words of the tile
 } gm_burnin_event_t;
+
+// What the per-tile compare accumulates in device memory over the compares of a run, zeroed
+// before the first one: 16 bytes of counters, then the log.
+typedef struct gm_burnin_state {
+  uint64_t total;   // differing 16-byte words
+  uint32_t cursor;  // events so far; the first min(cursor, GM_BURNIN_LOG_CAP) are in log[]
+  uint32_t pad;
+  gm_burnin_event_t log[GM_BURNIN_LOG_CAP];  // in the order the tiles' blocks took their slots
+} gm_burnin_state_t;
 
 typedef struct gm_burnin_inject {
   uint32_t id;     // < GM_CUSCAN_IDS
@@ -595,6 +614,21 @@ int gm_probe_mxgemm_nt_traced(int fmt, const void* A, const void* sA, const void
 // there too, so scratch must be 0.
 int gm_probe_gemm_nt_traced_info(int* num_regs, int* scratch_bytes);
 int gm_probe_mxgemm_nt_traced_info(int fmt, int* num_regs, int* scratch_bytes);
+// One per-tile compare on caller-owned device buffers, through the launch the burn-in's loop
+// uses: a and b are n × n bf16 results (b the reference), 16-byte aligned, n a positive multiple
+// of 256; cu and ref_cu the two CU maps, (n / 256)² words each; `iteration` goes into the
+// events. `state` is a gm_burnin_state_t (8-byte aligned, gm_probe_burn_in_state_bytes() bytes)
+// and exonerated, moved ((n / 256)² words each) and seen (GM_CUSCAN_IDS words) the three mark
+// arrays, all zeroed by the caller before the first call: they accumulate over calls as over
+// the iterations of a run (total and cursor grow, a mark once set stays set, events past the
+// log's capacity are counted in cursor only). A missing or misaligned pointer or a bad n:
+// hipErrorInvalidValue before any HIP call. Asynchronous on `stream`.
+int gm_probe_count_diff_tiles(const void* a, const void* b, int n, const uint32_t* cu,
+                              const uint32_t* ref_cu, uint32_t iteration, void* state,
+                              uint32_t* exonerated, uint32_t* moved, uint32_t* seen,
+                              void* stream);
+// sizeof(gm_burnin_state_t). Host only.
+uint64_t gm_probe_burn_in_state_bytes(void);
 // The attributed bf16 burn-in: gm_probe_burn_in_flip's arguments, operands and meanings of
 // *tflops, *mismatches and *iters, through the loop above. `inject` may be NULL. *attr and the
 // first min(attr->n_blamed, blamed_cap) entries of `blamed` are filled. Bad flips, an injection

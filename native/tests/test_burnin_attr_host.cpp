@@ -130,6 +130,22 @@ static void test_blame() {
     const GmBurninBlame b = gm_burnin_blame(ev, 1, ex.data(), tiles);
     EXPECT(b.blamed.size() == 1 && b.blamed[0].id == 0x077 && b.blamed[0].as_worker == 1);
   }
+  {  // W == R at a tile other units disagree with too: the reference's role, unless exonerated
+    for (int exonerated = 0; exonerated < 2; ++exonerated) {
+      std::vector<uint8_t> ex(tiles, (uint8_t)exonerated);
+      const gm_burnin_event_t ev[] = {{9, 7, 0x045, 0x045, 1}, {1, 7, 0x201, 0x045, 1},
+                                      {2, 7, 0x202, 0x045, 1}, {9, 8, 0x046, 0x046, 1},
+                                      {3, 6, 0x203, 0x046, 1}};
+      const GmBurninBlame b = gm_burnin_blame(ev, 5, ex.data(), tiles);
+      const gm_burnin_blamed_t *u = find(b, 0x045), *v = find(b, 0x046);
+      EXPECT(u && v);
+      if (!u || !v) continue;
+      // tile 8 has no witness but the unit itself; the event at tile 6 is another tile's
+      EXPECT(v->as_worker == 1u && v->events == (exonerated ? 1u : 2u));
+      EXPECT(u->as_reference == (exonerated ? 0u : 3u) && u->as_worker == (exonerated ? 1u : 0u));
+      EXPECT(u->events == (exonerated ? 1u : 3u));
+    }
+  }
   {  // the order: most events first, ties by id
     std::vector<uint8_t> ex(tiles, 1);
     const gm_burnin_event_t ev[] = {{1, 0, 9, 1, 1}, {1, 1, 4, 1, 1}, {2, 2, 7, 1, 1},

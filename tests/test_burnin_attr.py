@@ -40,6 +40,37 @@ def test_the_rotated_map_is_a_bijection_and_r0_is_todays_map(n, tiles):
     assert len({i * step % tiles for i in range(1, tiles + 1)}) == tiles
 
 
+def plain_map_mn(block, ntm, ntn):
+    """plain_map for a grid of ntm × ntn tiles: the tile as (row, column)."""
+    grid = ntm * ntn
+    q, rem, xcd = grid // 8, grid % 8, block % 8
+    wgid = block // 8 + sum(q + 1 if x < rem else q for x in range(xcd))
+    group, within = divmod(wgid, 8 * ntn)
+    rows = min(ntm - group * 8, 8)
+    return group * 8 + within % rows, within // rows
+
+
+@pytest.mark.parametrize("m,n", ((512, 768), (2304, 256), (768, 512), (256, 2304), (2560, 768)))
+def test_the_rotated_map_of_a_grid_that_is_not_square_is_a_bijection(m, n):
+    """On a square grid tm · (N / 256) + tn and tm · (M / 256) + tn are the same number. 2304 ×
+    256 and 2560 × 768 end in a group of fewer than 8 tile rows."""
+    lib, C = _native.probe(), _native.C
+    ntm, ntn = m // 256, n // 256
+    grid = ntm * ntn
+    tm, tn, step = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    for r in range(grid):
+        got = []
+        for b in range(grid):
+            assert lib.gm_probe_burn_in_tile_map(m, n, b, r, C.byref(tm), C.byref(tn),
+                                                 C.byref(step)) == 0
+            got.append((tm.value, tn.value))
+        assert sorted(got) == [(i, j) for i in range(ntm) for j in range(ntn)], (m, n, r)
+        assert got == [plain_map_mn((b + r) % grid, ntm, ntn) for b in range(grid)], (m, n, r)
+    assert gcd(step.value, grid) == 1 and (grid <= 8 or step.value % 8 != 0)
+    assert lib.gm_probe_burn_in_tile_map(m, n, 0, grid, C.byref(tm), C.byref(tn),
+                                         C.byref(step)) == 1
+
+
 def test_the_map_moves_every_tile_to_another_xcd_when_r_is_no_multiple_of_8():
     at0, _ = probe.burn_in_tile_map(2048, 0)
     block_of = {t: b for b, t in enumerate(at0)}
@@ -105,6 +136,29 @@ def test_a_unit_disagreeing_with_itself_is_blamed_as_the_worker():
         r = probe.burn_in_blame([(1, 0, 0x077, 0x077, 3)], [exonerated] * 4)
         (b,) = r["blamed"]
         assert b["id"] == 0x077 and b["as_worker"] == 1 and b["as_reference"] == 0
+
+
+def test_a_reference_that_its_own_cu_contradicts_too_is_still_blamed_as_the_reference():
+    """At r = 0 a block may land on the CU that computed the reference's tile. Where other units
+    contradict that reference as well and none reproduced it, the event is one more against the
+    reference, not a unit disagreeing with itself."""
+    others = [(i, 7, 0x200 + i, 0x045, 1) for i in range(1, 9)]
+    own = [(9, 7, 0x045, 0x045, 1)]
+    ex = [1] * 64
+    ex[7] = 0
+    for events in (others + own, own + others):                 # the order does not matter
+        (b,) = probe.burn_in_blame(events, ex)["blamed"]
+        assert b["id"] == 0x045 and b["as_reference"] == 9 and b["as_worker"] == 0
+    # the witnesses must be at that tile, and logged
+    (b,) = probe.burn_in_blame(own, ex)["blamed"]
+    assert b["id"] == 0x045 and b["as_worker"] == 1 and b["as_reference"] == 0
+    r = probe.burn_in_blame(own + [(1, 8, 0x201, 0x045, 1)], ex)
+    unit = {b["id"]: b for b in r["blamed"]}
+    assert unit[0x045]["as_worker"] == 1 and unit[0x201]["as_worker"] == 1
+    # an exonerated tile stands: whoever differs from it there is blamed as the worker
+    r = probe.burn_in_blame(others + own, [1] * 64)
+    unit = {b["id"]: b for b in r["blamed"]}
+    assert unit[0x045]["as_worker"] == 1 and unit[0x045]["as_reference"] == 0 and len(unit) == 9
 
 
 def test_blamed_units_are_sorted_by_events_then_id():
@@ -216,6 +270,110 @@ def test_native_entries_refuse_before_selecting_a_device():
     assert lib.gm_probe_gemm_nt_traced(None, None, None, 256, 256, 64, 0, None, None, None) == 1
     assert lib.gm_probe_mxgemm_nt_traced(0, None, None, None, None, None, 256, 256, 128, 0, None,
                                          None, None) == 1
+
+
+# ---------------------------------------------------------------------------- the compare's seam
+def test_the_published_state_is_the_one_the_library_uses():
+    C = _native.C
+    assert _native.probe().gm_probe_burn_in_state_bytes() == probe.BURN_IN_STATE_BYTES
+    assert probe.BURN_IN_STATE_BYTES == 16 + 20 * _native.BURNIN_LOG_CAP
+    s = _native.BurninState
+    assert (s.total.offset, s.cursor.offset, s.log.offset) == (0, 8, 16)
+    assert C.sizeof(_native.BurninEvent) == 20
+
+
+def test_count_diff_tiles_refuses_before_the_native_call(monkeypatch):
+    torch = pytest.importorskip("torch")
+    monkeypatch.setattr(_native, "probe", lambda: pytest.fail("the native library was reached"))
+    bf, i32 = torch.bfloat16, torch.int32
+    a, b = torch.zeros(512, 512, dtype=bf), torch.zeros(512, 512, dtype=bf)
+    cu, ref = torch.zeros(4, dtype=i32), torch.zeros(4, dtype=i32)
+
+    def state(nbytes=probe.BURN_IN_STATE_BYTES, exonerated=4, moved=4, seen=_native.CUSCAN_IDS):
+        return probe.CompareState(torch.zeros(nbytes, dtype=torch.uint8),
+                                  *(torch.zeros(k, dtype=i32) for k in (exonerated, moved, seen)))
+
+    wide = torch.zeros(512, 1024, dtype=bf)
+    for args, kw, why in (
+            ((a.float(), b, cu, ref, 1), {}, "2-D bf16"),                       # dtype
+            ((a, b.view(torch.int16), cu, ref, 1), {}, "2-D bf16"),
+            ((a.view(-1), b.view(-1), cu, ref, 1), {}, "2-D bf16"),
+            ((a, wide[:, ::2], cu, ref, 1), {}, "contiguous"),                  # strided
+            ((a.t(), b, cu, ref, 1), {}, "contiguous"),
+            ((torch.zeros(300, 300, dtype=bf),) * 2 + (cu, ref, 1), {}, "multiple of 256"),
+            ((torch.zeros(0, 0, dtype=bf),) * 2 + (cu, ref, 1), {}, "multiple of 256"),
+            ((a, torch.zeros(256, 256, dtype=bf), cu, ref, 1), {}, "multiple of 256"),
+            ((wide, wide, cu, ref, 1), {}, "multiple of 256"),                  # not square
+            ((a, b, cu, ref, -1), {}, "iteration"),
+            ((a, b, cu, ref, 1 << 32), {}, "iteration"),
+            ((a, b, cu, ref, True), {}, "iteration"),
+            ((a, b, torch.zeros(9, dtype=i32), ref, 1), {}, "cu has 9 entries, not 4"),
+            ((a, b, cu, torch.zeros(3, dtype=i32), 1), {}, "ref_cu has 3 entries, not 4"),
+            ((a, b, cu.to(torch.int64), ref, 1), {}, "cu must be a contiguous int32"),
+            ((a, b, cu, ref.float(), 1), {}, "ref_cu must be a contiguous int32"),
+            ((a, b, cu, torch.zeros(8, dtype=i32)[::2], 1), {}, "ref_cu must be a contiguous"),
+            ((a, b, [0] * 4, ref, 1), {}, "cu must be a contiguous int32"),
+            ((a, b, cu, ref, 1), {"state": state(nbytes=probe.BURN_IN_STATE_BYTES - 20)},
+             "exactly"),                                                        # the state
+            ((a, b, cu, ref, 1), {"state": state(nbytes=probe.BURN_IN_STATE_BYTES + 64)},
+             "exactly"),
+            ((a, b, cu, ref, 1), {"state": state(exonerated=9)}, "exonerated has 9"),
+            ((a, b, cu, ref, 1), {"state": state(moved=3)}, "moved has 3"),
+            ((a, b, cu, ref, 1), {"state": state(seen=256)}, "seen has 256"),
+            ((a, b, cu, ref, 1), {"state": tuple(state())}, "CompareState"),
+            ((a, b, cu, ref, 1), {"state": state()}, "HIP device"),             # all else is right
+            ((a, b, cu, ref, 1), {}, "HIP device")):
+        with pytest.raises(ProbeError, match=why):
+            probe.count_diff_tiles(*args, **kw)
+
+
+def test_native_count_diff_tiles_refuses_before_any_hip_call():
+    """Null, misaligned, bad n: 1 (hipErrorInvalidValue). Every pointer here is a host address,
+    so a launch that got past the checks would not return quietly."""
+    lib, C = _native.probe(), _native.C
+    buf = (C.c_uint8 * 4096)()
+    p = (C.addressof(buf) + 63) & ~63                   # 64-byte aligned, 4000 bytes behind it
+    good = [p, p + 64, 256, p + 128, p + 192, 1, p + 256, p + 320, p + 384, p + 448, None]
+    assert lib.gm_probe_count_diff_tiles.argtypes[2] is C.c_int
+    for at, bad in ([(i, None) for i in (0, 1, 3, 4, 6, 7, 8, 9)] +
+                    [(0, p + 8), (1, p + 64 + 2), (3, p + 128 + 1), (4, p + 192 + 2),
+                     (6, p + 256 + 4), (7, p + 320 + 1), (8, p + 384 + 2), (9, p + 448 + 3)] +
+                    [(2, n) for n in (0, -256, 100, 255, 257, 768 + 128, (1 << 31) - 256)]):
+        args = list(good)
+        args[at] = bad
+        assert lib.gm_probe_count_diff_tiles(*args) == 1, (at, bad)
+
+
+# ---------------------------------------------------------------------------- the tests' model
+def test_the_numpy_model_of_the_compare_on_a_case_written_out_by_hand():
+    """tests/test_burnin_compare_gpu.py checks the kernel against its ``tile_words``; this pins
+    that model: 512 × 512, tiles 0 1 / 2 3, every count below worked out by hand."""
+    np = pytest.importorskip("numpy")
+    pytest.importorskip("torch")
+    from test_burnin_compare_gpu import tile_words
+
+    a = np.random.default_rng(1).integers(0, 1 << 16, size=(512, 512), dtype=np.uint16)
+    assert tile_words(a, a).tolist() == [0, 0, 0, 0]
+    b = a.copy()
+    b[0, 0] ^= 1            # tile 0, row 0, word 0
+    b[0, 7] ^= 0x8000       # the same word: its last element
+    b[0, 8] ^= 1            # tile 0, row 0, word 1
+    b[255, 255] ^= 2        # tile 0's last word
+    b[255, 256] ^= 2        # tile 1, row 255, word 0: the next 16 bytes in memory
+    b[256, 255] ^= 4        # tile 2, row 0, its last word
+    b[511, 504] ^= 4        # tile 3's last word, first element
+    b[511, 511] ^= 4        # ... and last
+    b[300, 16:32] ^= 0x10   # tile 2, row 44: words 2 and 3 in full
+    assert tile_words(a, b).tolist() == [3, 1, 3, 1]
+    assert tile_words(b, a).tolist() == [3, 1, 3, 1]
+    b = a ^ np.uint16(0x0100)                           # every element
+    assert tile_words(a, b).tolist() == [8192] * 4
+    b[256:, :256] = a[256:, :256]                       # but tile 2
+    assert tile_words(a, b).tolist() == [8192, 8192, 0, 8192]
+    c = np.zeros((768, 768), dtype=np.uint16)
+    d = c.copy()
+    d[256 + 5, 512 + 9] = 1                             # 3 × 3: tile 1 · 3 + 2
+    assert tile_words(c, d).tolist() == [0, 0, 0, 0, 0, 1, 0, 0, 0]
 
 
 # ---------------------------------------------------------------------------- the wiring
