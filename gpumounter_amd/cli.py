@@ -59,6 +59,8 @@ import os
 import sys
 from typing import List, Optional
 
+from gpumounter_amd import burnin_options
+
 
 def _cfg(args, **over):
     from gpumounter_amd.utils.config import Config
@@ -198,61 +200,12 @@ def _memtest_arg(kind):
     return conv
 
 
-def _burn_in_flip(text):
-    """argparse type for --burn-in-flip: the parser in ops.probe, its refusal a usage error."""
-    from gpumounter_amd.ops import probe
-    try:
-        return probe.parse_burn_in_flip(text)
-    except probe.ProbeError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
-
-
-def _burn_in_formats(text):
-    """argparse type for --burn-in-format: the parser in ops.mxgemm, its refusal a usage error."""
-    from gpumounter_amd.ops import mxgemm
-    try:
-        return mxgemm.parse_burn_in_formats(text)
-    except mxgemm.ProbeError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
-
-
-def _add_burn_in_format(p) -> None:
-    p.add_argument("--burn-in-format", type=_burn_in_formats, default=None, metavar="LIST",
-                   help="with --burn-in: the burn-in's formats, of bf16,mxfp8,mxfp4 (default "
-                        "bf16); each runs for SECONDS, the block-scaled ones as a bit-checked "
-                        "fp8 / fp4 GEMM on the MX matrix pipe")
-    p.add_argument("--burn-in-attribute", action="store_true",
-                   help="with --burn-in: rotate the GEMM's tiles over the blocks from one "
-                        "iteration to the next, so other XCDs and CUs recompute every tile, "
-                        "record the CU of every block and name the units behind a mismatch")
-    p.add_argument("--burn-in-inject", type=_burn_in_inject, default=None, metavar="ID|first:MASK",
-                   help="with --burn-in-attribute: negative control: every block on that CU "
-                        "(first: the one that computed tile 0 in the warm-up) XORs MASK into "
-                        "one element of its tile, in the reference too; the burn-in must fail "
-                        "and name that unit alone")
-
-
-def _burn_in_inject(text):
-    """argparse type for --burn-in-inject: the parser in ops.probe, its refusal a usage error."""
-    from gpumounter_amd.ops import probe
-    try:
-        return probe.parse_burn_in_inject(text)
-    except probe.ProbeError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
-
-
-def _burn_in_usage(args, tool: str) -> str:
-    """What is wrong with the burn-in's options, or ""."""
-    older = [("--burn-in-flip", args.burn_in_flip), ("--burn-in-format", args.burn_in_format)]
-    if tool == "doctor":              # it has always named the format first
-        older.reverse()
-    for option, value in older + [("--burn-in-attribute", args.burn_in_attribute),
-                                  ("--burn-in-inject", args.burn_in_inject)]:
-        if value and not args.burn_in:
-            return f"{tool}: {option} needs --burn-in SECONDS"
-    if args.burn_in_inject and not args.burn_in_attribute:
-        return f"{tool}: --burn-in-inject needs --burn-in-attribute"
-    return ""
+def _burn_in_usage(args, tool: str) -> int:
+    """2 with the usage error printed if the burn-in's options do not go together, else 0."""
+    error = burnin_options.usage(args, format_first=tool == "doctor")
+    if error:
+        print(f"{tool}: {error}", file=sys.stderr)
+    return 2 if error else 0          # a usage error, not a failed burn-in (exit 1)
 
 
 def _atomics_arg(kind):
@@ -405,10 +358,8 @@ def _add_memtest_size(p, what: str) -> None:
 def cmd_probe(args) -> int:
     from gpumounter_amd.ops import probe
 
-    error = _burn_in_usage(args, "probe")
-    if error:
-        print(error, file=sys.stderr)
-        return 2                      # a usage error, not a failed burn-in (exit 1)
+    if _burn_in_usage(args, "probe"):
+        return 2
     cu, *later = _scans()             # the CU scan: before the host-link and atomics tests
     error = _scan_usage(cu, args, "probe")
     if error:
@@ -678,9 +629,7 @@ def cmd_doctor(args) -> int:
     if args.atomics_inject and not args.atomics:
         print("doctor: --atomics-inject needs --atomics", file=sys.stderr)
         return 2
-    error = _burn_in_usage(args, "doctor")
-    if error:
-        print(error, file=sys.stderr)
+    if _burn_in_usage(args, "doctor"):
         return 2
     for value, name in ((args.burn_in_format, "burn_in_formats"),
                         (args.burn_in_flip, "burn_in_flip"),
@@ -742,13 +691,8 @@ def build_parser() -> argparse.ArgumentParser:
     p = sub.add_parser("probe")
     p.add_argument("--bdf", action="append")
     p.add_argument("--full", action="store_true")
-    p.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
-                   help="sustained GEMM load with bit-exact result checks (exit 1 on mismatch)")
-    p.add_argument("--burn-in-flip", type=_burn_in_flip, action="append", default=None,
-                   metavar="ELEM:MASK",
-                   help="negative control (repeatable): XOR that bf16 element of the burn-in's "
-                        "reference result with MASK; the burn-in must fail")
-    _add_burn_in_format(p)
+    burnin_options.add_options(p, "sustained GEMM load with bit-exact result checks (exit 1 on "
+                                  "mismatch)")
     _add_memtest_size(p, "HBM pattern test over SIZE bytes (64M, 8G; default: 90 %% of the free "
                          "memory) of every probed GPU (exit 1 on any bad word)")
     p.add_argument("--memtest-passes", type=int, default=1, metavar="N")
@@ -819,12 +763,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="skip the kubelet and apiserver checks")
     p.add_argument("--gpu", action="store_true",
                    help="also run the gfx950 liveness kernel on every GPU")
-    p.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
-                   help="with --gpu: sustained bit-checked GEMM load per GPU")
-    p.add_argument("--burn-in-flip", type=_burn_in_flip, action="append", default=None,
-                   metavar="ELEM:MASK",
-                   help="the burn-in's negative control (repeatable), for every chosen format")
-    _add_burn_in_format(p)
+    burnin_options.add_options(p, "with --gpu: sustained bit-checked GEMM load per GPU")
     _add_memtest_size(p, "with --gpu: HBM pattern test over SIZE bytes per GPU (default: 90 %% of "
                          "its free memory)")
     _add_doctor_scan(p, cu)

@@ -105,10 +105,9 @@ def _operand(t, what: str, rows: Optional[int], cols: int):
         raise ProbeError(f"mxgemm: {what}'s storage is not 16-byte aligned")
 
 
-def gemm_nt(fmt: str, a, sa, bt, sb, out=None, stream=None):
-    """C (bf16 [M, N]) = A · Btᵀ for packed operands and their scales on a HIP device (the
-    layouts of :func:`fill`). M and N multiples of 256; K = 32 × the scales' columns, a multiple
-    of the format's K-tile. Asynchronous."""
+def _operands(fmt: str, a, sa, bt, sb, out):
+    """The packed operands, their scales and ``out`` (made if None) of one GEMM, checked:
+    (M, N, K, out)."""
     import torch
 
     _fmt(fmt)
@@ -128,6 +127,16 @@ def gemm_nt(fmt: str, a, sa, bt, sb, out=None, stream=None):
     elif (not isinstance(out, torch.Tensor) or out.shape != (m, n) or out.dtype != torch.bfloat16
           or not out.is_contiguous() or out.device != a.device):
         raise ProbeError(f"mxgemm: out must be a contiguous bf16 [{m}, {n}] tensor on {a.device}")
+    return m, n, k, out
+
+
+def gemm_nt(fmt: str, a, sa, bt, sb, out=None, stream=None):
+    """C (bf16 [M, N]) = A · Btᵀ for packed operands and their scales on a HIP device (the
+    layouts of :func:`fill`). M and N multiples of 256; K = 32 × the scales' columns, a multiple
+    of the format's K-tile. Asynchronous."""
+    import torch
+
+    m, n, k, out = _operands(fmt, a, sa, bt, sb, out)
     with torch.cuda.device(a.device):
         _check(_native.probe().gm_probe_mxgemm_nt(FORMAT_CODE[fmt], a.data_ptr(), sa.data_ptr(),
                                                   bt.data_ptr(), sb.data_ptr(), out.data_ptr(),
@@ -176,29 +185,9 @@ def gemm_nt_traced(fmt: str, a, sa, bt, sb, r: int = 0, out=None, _inject=None, 
     cu_of_tile), as :func:`probe.gemm_nt_traced`. Asynchronous."""
     import torch
 
-    _fmt(fmt)
-    for t, what in ((a, "A"), (sa, "sA"), (bt, "Bt"), (sb, "sB")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise ProbeError(f"mxgemm: {what} must be a 2-D uint8 torch tensor")
-    m, n, k = int(a.shape[0]), int(bt.shape[0]), int(sa.shape[1]) * BLOCK
-    check_shape(fmt, m, n, k)
-    _operand(a, "A", m, row_bytes(fmt, k))
-    _operand(bt, "Bt", n, row_bytes(fmt, k))
-    _operand(sa, "sA", m, k // BLOCK)
-    _operand(sb, "sB", n, k // BLOCK)
-    if len({t.device for t in (a, sa, bt, sb)}) != 1:
-        raise ProbeError("mxgemm: the operands are on different devices")
+    m, n, k, out = _operands(fmt, a, sa, bt, sb, out)
     grid = (m // TILE_MN) * (n // TILE_MN)
-    if not isinstance(r, int) or isinstance(r, bool) or not 0 <= r < grid:
-        raise ProbeError(f"mxgemm traced: rotation {r!r} is not in [0, {grid})")
-    inj = probe._burn_in_inject(_inject, True)
-    if inj is not None and inj.first:
-        raise ProbeError("mxgemm traced: one GEMM has no warm-up to take 'first' from")
-    if out is None:
-        out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
-    elif (not isinstance(out, torch.Tensor) or out.shape != (m, n) or out.dtype != torch.bfloat16
-          or not out.is_contiguous() or out.device != a.device):
-        raise ProbeError(f"mxgemm: out must be a contiguous bf16 [{m}, {n}] tensor on {a.device}")
+    inj = probe._traced_args("mxgemm traced", r, grid, _inject)
     cus = torch.full((grid,), -1, dtype=torch.int32, device=a.device)
     with torch.cuda.device(a.device):
         _check(_native.probe().gm_probe_mxgemm_nt_traced(
@@ -219,19 +208,8 @@ def burn_in(dev: int, seconds: float, fmt: str, n: int = 8192,
     check_shape(fmt, n, n, n)
     if not isinstance(seconds, (int, float)) or isinstance(seconds, bool) or not seconds > 0:
         raise ProbeError(f"mx burn-in: seconds = {seconds!r} is not a positive number")
-    elems, fe, fm = probe._burn_in_flips(_flips, n)
-    inj = probe._burn_in_inject(_inject, attribute)
-    if attribute:
-        out = probe._run_attributed(f"{fmt} burn-in", _native.probe().gm_probe_mx_burn_in_attr,
-                                    (dev, FORMAT_CODE[fmt]), dev, n, seconds, elems, fe, fm, inj)
-        out["format"] = fmt
-        return out
-    tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
-    _check(_native.probe().gm_probe_mx_burn_in_flip(dev, FORMAT_CODE[fmt], n, seconds,
-                                                    len(elems), fe, fm, C.byref(tf),
-                                                    C.byref(bad), C.byref(it)),
-           f"{fmt} burn-in")
-    out = probe._burn_in_report(dev, n, seconds, elems, tf, bad, it)
+    out = probe._run_burn_in(f"{fmt} burn-in", "gm_probe_mx_burn_in", (dev, FORMAT_CODE[fmt]), dev,
+                             n, seconds, _flips, attribute, _inject)
     out["format"] = fmt
     return out
 

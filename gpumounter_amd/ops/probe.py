@@ -186,20 +186,15 @@ def gemm_bf16(a, b, out=None, stream=None):
     return out
 
 
-def gemm_nt(a, bt, out=None, stream=None, variant: Optional[int] = None):
-    """C(bf16) = A @ Btᵀ for bf16 torch tensors on a HIP device: the 256²-tile
-    global_load_lds MFMA GEMM (gm_probe_gemm_nt). Shapes: A [M,K], Bt [N,K] contiguous
-    (both K-major); M, N multiples of 256 and K a multiple of 64. ``variant`` picks a schedule
-    (0: per-k-step fragment reads, 1: whole K-tile of reads up front, 2: quadrant phases,
-    3: V1 on 32x32x16, 4: 4 waves × 128², 5: local-read prefetch across the barrier, 6: V4 on
-    V5's schedule with buffer_load-to-LDS staging, 7: V5 with buffer_load-to-LDS staging, 8: V5 with a DPP-transposed 8-byte-store epilogue, 9: V2 with register prefetch across phases;
-    default: the fastest measured, 5 — profiles/history/r1_gemm)."""
+def _nt_operands(what: str, a, bt, out):
+    """A bf16 NT operand pair, A [M,K] and Bt [N,K], and ``out`` (made if None), checked for the
+    256²-tile GEMM: (M, N, K, out)."""
     import torch
 
     if a.dtype != torch.bfloat16 or bt.dtype != torch.bfloat16:
-        raise ProbeError("gemm_nt expects bf16 inputs")
+        raise ProbeError(f"{what} expects bf16 inputs")
     if not (a.is_contiguous() and bt.is_contiguous()):
-        raise ProbeError("gemm_nt expects contiguous inputs")
+        raise ProbeError(f"{what} expects contiguous inputs")
     m, k = a.shape
     n, k2 = bt.shape
     if k != k2 or m % 256 or n % 256 or k % 64:
@@ -207,7 +202,19 @@ def gemm_nt(a, bt, out=None, stream=None, variant: Optional[int] = None):
     if out is None:
         out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
     elif out.shape != (m, n) or out.dtype != torch.bfloat16 or not out.is_contiguous():
-        raise ProbeError("gemm_nt: out must be a contiguous bf16 [M,N] tensor")
+        raise ProbeError(f"{what}: out must be a contiguous bf16 [M,N] tensor")
+    return m, n, k, out
+
+
+def gemm_nt(a, bt, out=None, stream=None, variant: Optional[int] = None):
+    """C(bf16) = A @ Btᵀ for bf16 torch tensors on a HIP device: the 256²-tile
+    global_load_lds MFMA GEMM (gm_probe_gemm_nt). Shapes: A [M,K], Bt [N,K] contiguous
+    (both K-major); M, N multiples of 256 and K a multiple of 64. ``variant`` picks a schedule
+    (1: whole K-tile of fragment reads up front, 5: local-read prefetch across the barrier;
+    default: the faster, 5 — profiles/history/r1_gemm)."""
+    import torch
+
+    m, n, k, out = _nt_operands("gemm_nt", a, bt, out)
     s = stream if stream is not None else torch.cuda.current_stream(a.device)
     with torch.cuda.device(a.device):
         lib = _native.probe()
@@ -336,17 +343,24 @@ def _attribution(attr, blamed) -> Dict:
     return out
 
 
-def _run_attributed(what: str, entry, lead: tuple, dev: int, n: int, seconds: float, elems,
-                    fe, fm, inj) -> Dict:
-    """One attributed burn-in through ``entry`` (``lead``: what it takes before ``n``)."""
+def _run_burn_in(what: str, stem: str, lead: tuple, dev: int, n: int, seconds: float, _flips,
+                 attribute: bool, _inject) -> Dict:
+    """One burn-in through the native entry point ``{stem}_flip`` or, attributed, ``{stem}_attr``
+    (``lead``: what they take before ``n``): the controls checked, the call, the report."""
+    elems, fe, fm = _burn_in_flips(_flips, n)
+    inj = _burn_in_inject(_inject, attribute)
     tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
-    attr = _native.BurninAttr()
-    blamed = (_native.BurninBlamed * _native.BURNIN_LOG_CAP)()
-    _check(entry(*lead, n, seconds, len(elems), fe, fm, C.byref(inj) if inj else None,
-                 C.byref(tf), C.byref(bad), C.byref(it), C.byref(attr), blamed, len(blamed)),
-           what)
+    args, outs = (*lead, n, seconds, len(elems), fe, fm), (C.byref(tf), C.byref(bad), C.byref(it))
+    if attribute:
+        attr = _native.BurninAttr()
+        blamed = (_native.BurninBlamed * _native.BURNIN_LOG_CAP)()
+        _check(getattr(_native.probe(), f"{stem}_attr")(
+            *args, C.byref(inj) if inj else None, *outs, C.byref(attr), blamed, len(blamed)), what)
+    else:
+        _check(getattr(_native.probe(), f"{stem}_flip")(*args, *outs), what)
     out = _burn_in_report(dev, n, seconds, elems, tf, bad, it)
-    out["attribution"] = _attribution(attr, blamed)
+    if attribute:
+        out["attribution"] = _attribution(attr, blamed)
     return out
 
 
@@ -408,6 +422,17 @@ def burn_in_blame(events: Sequence[Tuple[int, int, int, int, int]], exonerated: 
             "blamed": units, "first_events": _first_events(attr)}
 
 
+def _traced_args(what: str, r, grid: int, _inject) -> Optional[_native.BurninInject]:
+    """What one traced GEMM takes besides its operands, checked: the rotation, and the injection
+    (returned as the native struct, or None)."""
+    if not isinstance(r, int) or isinstance(r, bool) or not 0 <= r < grid:
+        raise ProbeError(f"{what}: rotation {r!r} is not in [0, {grid})")
+    inj = _burn_in_inject(_inject, True)
+    if inj is not None and inj.first:
+        raise ProbeError(f"{what}: one GEMM has no warm-up to take 'first' from")
+    return inj
+
+
 def gemm_nt_traced(a, bt, r: int = 0, out=None, _inject=None, stream=None):
     """:func:`gemm_nt` through the attributed burn-in's kernel at rotation ``r``: (C, cu_of_tile),
     ``cu_of_tile`` an int32 device tensor with the 12-bit id of the CU that computed each tile,
@@ -415,24 +440,9 @@ def gemm_nt_traced(a, bt, r: int = 0, out=None, _inject=None, stream=None):
     their tile. Asynchronous."""
     import torch
 
-    if a.dtype != torch.bfloat16 or bt.dtype != torch.bfloat16:
-        raise ProbeError("gemm_nt_traced expects bf16 inputs")
-    if not (a.is_contiguous() and bt.is_contiguous()):
-        raise ProbeError("gemm_nt_traced expects contiguous inputs")
-    m, k = a.shape
-    n, k2 = bt.shape
-    if k != k2 or m % 256 or n % 256 or k % 64:
-        raise ProbeError(f"unsupported shape A{tuple(a.shape)} Bt{tuple(bt.shape)}")
+    m, n, k, out = _nt_operands("gemm_nt_traced", a, bt, out)
     grid = (m // 256) * (n // 256)
-    if not isinstance(r, int) or isinstance(r, bool) or not 0 <= r < grid:
-        raise ProbeError(f"gemm_nt_traced: rotation {r!r} is not in [0, {grid})")
-    inj = _burn_in_inject(_inject, True)
-    if inj is not None and inj.first:
-        raise ProbeError("gemm_nt_traced: one GEMM has no warm-up to take 'first' from")
-    if out is None:
-        out = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
-    elif out.shape != (m, n) or out.dtype != torch.bfloat16 or not out.is_contiguous():
-        raise ProbeError("gemm_nt_traced: out must be a contiguous bf16 [M,N] tensor")
+    inj = _traced_args("gemm_nt_traced", r, grid, _inject)
     cus = torch.full((grid,), -1, dtype=torch.int32, device=a.device)
     with torch.cuda.device(a.device):
         _check(_native.probe().gm_probe_gemm_nt_traced(
@@ -472,16 +482,8 @@ def burn_in(dev: int, seconds: float = 10.0, n: int = 8192,
     (native/include/gm_probe.h, "attributed burn-in"). ``_inject=(id or "first", mask)`` is its
     negative control: every block on that CU XORs ``mask`` into element (0, 0) of its tile, in
     the reference too; ``"first"`` is the CU that computed tile 0 in the warm-up."""
-    elems, fe, fm = _burn_in_flips(_flips, n)
-    inj = _burn_in_inject(_inject, attribute)
-    if attribute:
-        return _run_attributed("burn-in", _native.probe().gm_probe_burn_in_attr, (dev,), dev, n,
-                               seconds, elems, fe, fm, inj)
-    tf, bad, it = C.c_double(0), C.c_uint64(0), C.c_int(0)
-    _check(_native.probe().gm_probe_burn_in_flip(dev, n, seconds, len(elems), fe, fm,
-                                                 C.byref(tf), C.byref(bad), C.byref(it)),
-           "burn-in")
-    return _burn_in_report(dev, n, seconds, elems, tf, bad, it)
+    return _run_burn_in("burn-in", "gm_probe_burn_in", (dev,), dev, n, seconds, _flips, attribute,
+                        _inject)
 
 
 def _dev_bytes(t, what: str, align: int = 16, multiple: int = 16) -> int:

@@ -51,7 +51,8 @@ import os
 import sys
 from typing import Dict, List
 
-from gpumounter_amd.ops import cuframe
+from gpumounter_amd import burnin_options
+from gpumounter_amd.ops import cuframe, mxgemm
 from gpumounter_amd.ops.probe import ProbeError
 
 
@@ -114,20 +115,8 @@ def main(argv=None) -> int:
                     help="skip the GPU checks; all-reduce over N gloo ranks on the CPU")
     ap.add_argument("--numel", type=int, default=1 << 24, help="all-reduce elements (bf16)")
     ap.add_argument("--no-p2p", action="store_true")
-    ap.add_argument("--burn-in", type=float, default=0.0, metavar="SECONDS",
-                    help="then load every GPU at once with bit-checked GEMMs for SECONDS")
-    ap.add_argument("--burn-in-format", default=None, metavar="LIST",
-                    help="the burn-in's formats, of bf16,mxfp8,mxfp4 (default bf16), one after the "
-                         "other for SECONDS each; needs --burn-in")
-    ap.add_argument("--burn-in-flip", action="append", default=None, metavar="ELEM:MASK",
-                    help="the burn-in's negative control, for every chosen format (see probe "
-                         "--burn-in-flip); needs --burn-in")
-    ap.add_argument("--burn-in-attribute", action="store_true",
-                    help="the burn-in with its tiles rotated over the CUs, naming the units "
-                         "behind a mismatch (see probe --burn-in-attribute); needs --burn-in")
-    ap.add_argument("--burn-in-inject", default=None, metavar="ID|first:MASK",
-                    help="its negative control (see probe --burn-in-inject); needs "
-                         "--burn-in-attribute")
+    burnin_options.add_options(ap, "then load every GPU at once with bit-checked GEMMs for "
+                                   "SECONDS, one format after the other")
     ap.add_argument("--memtest", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the HBM pattern test on every GPU at once over SIZE bytes each "
                          "(64M, 8G; default: 90 %% of the free memory)")
@@ -161,31 +150,12 @@ def main(argv=None) -> int:
                 for name, text in texts.items()}
         except ProbeError as e:
             ap.error(str(e))
-    burn_in_formats, burn_in_flips = ("bf16",), None
-    if args.burn_in_format is not None or args.burn_in_flip is not None:
-        from gpumounter_amd.ops import mxgemm, probe as _probe
-        if not args.burn_in:
-            ap.error("--burn-in-format and --burn-in-flip need --burn-in SECONDS")
-        try:
-            if args.burn_in_format is not None:
-                burn_in_formats = mxgemm.parse_burn_in_formats(args.burn_in_format)
-            if args.burn_in_flip is not None:
-                burn_in_flips = [_probe.parse_burn_in_flip(t) for t in args.burn_in_flip]
-        except ProbeError as e:
-            ap.error(str(e))
-    burn_in_more: Dict = {}           # the attributed mode's keywords, none unless asked for
-    if args.burn_in_attribute or args.burn_in_inject is not None:
-        from gpumounter_amd.ops import mxgemm, probe as _probe
-        if not args.burn_in:
-            ap.error("--burn-in-attribute and --burn-in-inject need --burn-in SECONDS")
-        if not args.burn_in_attribute:
-            ap.error("--burn-in-inject needs --burn-in-attribute")
-        try:
-            inject = (None if args.burn_in_inject is None
-                      else _probe.parse_burn_in_inject(args.burn_in_inject))
-        except ProbeError as e:
-            ap.error(str(e))
-        burn_in_more = mxgemm.attribute_kwargs(True, inject)
+    error = burnin_options.usage(args, name_pair=True)
+    if error:
+        ap.error(error)
+    burn_in_formats, burn_in_flips = args.burn_in_format or ("bf16",), args.burn_in_flip
+    # the attributed mode's keywords, none unless asked for
+    burn_in_more = mxgemm.attribute_kwargs(args.burn_in_attribute, args.burn_in_inject)
     atomics_inject = None
     if args.atomics_inject is not None:
         from gpumounter_amd.ops import atomics
@@ -239,8 +209,6 @@ def main(argv=None) -> int:
     report["ok"] &= report["allreduce"]["ok"]
     if args.burn_in and not args.cpu_ranks:
         from concurrent.futures import ThreadPoolExecutor
-
-        from gpumounter_amd.ops import mxgemm
 
         # all GPUs at once (shared power/thermal envelope); ctypes drops the GIL in the call
         for fmt in burn_in_formats:

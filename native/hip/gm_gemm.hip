@@ -17,26 +17,16 @@ namespace {
 //     64 KiB, the next stage's DMA issued before the current stage's MFMAs;
 //   * LDS image lane-linear (one 1 KiB wave instruction = 8 rows × 128 B); bank conflicts of the
 //     16-row ds_read_b128 fragment reads are removed by an XOR swizzle of the 16-B chunk index
-//     with (row>>1)&7, applied to the per-lane GLOBAL source address and to the LDS read address;
+//     with (row>>1)&7, applied to the per-lane GLOBAL source address and to the LDS read address
+//     (TileLane, gm_gemm_shared.h, which holds everything here but the schedules);
 //   * blockIdx remapped bijectively so each XCD runs a contiguous range of tiles, grouped 8 tile
 //     rows deep, so concurrently running blocks of one XCD share A/B panels in that XCD's L2.
 namespace g256 {
-constexpr int TM = 256, TN = 256, TK = 64, kThreads = 512, kGroupM = 8;
-constexpr int kTileBytes = TM * TK * 2;       // 32 KiB: one operand, one stage
-constexpr int kStageBytes = 2 * kTileBytes;   // A + Bt
+using namespace tile256;                      // the geometry itself: gm_gemm_shared.h
+constexpr int TK = kRowBytes / 2;             // 64 bf16
 constexpr int kLdsBytes = 2 * kStageBytes;    // two stages: 128 KiB of the 160 KiB LDS
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) void gbl_void;
 }  // namespace g256
 constexpr int kGemmNtDefault = 5;  // profiles/history/r1_gemm: V5 +2.9 % over V1 at 4096³, +0.9 % at 8192³
-
-// The block → tile map (gm_gemm_shared.h) at this kernel's geometry.
-__device__ __forceinline__ void gemm_tile_of(int M, int N, int& tm, int& tn) {
-  gemm_tile_of<g256::TM, g256::TN, g256::kGroupM>(M, N, tm, tn);
-}
-__device__ __forceinline__ void gemm_tile_of(int M, int N, int& tm, int& tn, int r) {
-  gemm_tile_of<g256::TM, g256::TN, g256::kGroupM>(M, N, tm, tn, r);
-}
 
 // V1 — the plain schedule, kept as the reference point for V5: all 24 fragment reads of the
 // 64-deep K-tile are issued up front, so the second k-step's reads overlap the first step's
@@ -46,44 +36,17 @@ __global__ __launch_bounds__(512) void k_gemm_nt256(const __bf16* __restrict__ A
                                                     __bf16* __restrict__ C, int M, int N, int K) {
   using namespace g256;
   __shared__ __attribute__((aligned(1024))) char lds[kLdsBytes];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-
+  const TileLane c = tile_lane();
   int tm, tn;
-  gemm_tile_of(M, N, tm, tn);
-
-  // Staging: wave w moves 1 KiB chunks c = w + 8i (i = 0..3) of each operand's 256×64 tile.
-  // Lane l writes LDS byte c*1024 + l*16 = row 8c + (l>>3), slot l&7, which holds logical
-  // 16-B chunk (l&7) ^ ((row>>1)&7). (row>>1)&7 is the same for all i (rows differ by 64).
-  const int srow = 8 * wave + (lane >> 3);
-  const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
-  const __bf16* a_src = A + (size_t)(tm * TM + srow) * K + schunk * 8;
-  const __bf16* b_src = Bt + (size_t)(tn * TN + srow) * K + schunk * 8;
+  tile_pick<false>(M, N, GemmTrace{}, tm, tn);
+  const __bf16* a_src = tile_src(c, A, tm * TM, K);
+  const __bf16* b_src = tile_src(c, Bt, tn * TN, K);
   const size_t row64 = (size_t)64 * K;
-
   auto stage = [&](int buf, int k0) {
-    char* base = lds + buf * kStageBytes + wave * 1024;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      __builtin_amdgcn_global_load_lds((gbl_void*)(a_src + i * row64 + k0),
-                                       (lds_void*)(base + i * 8192), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gbl_void*)(b_src + i * row64 + k0),
-                                       (lds_void*)(base + kTileBytes + i * 8192), 16, 0, 0);
-    }
+    tile_stage(c, lds + buf * kStageBytes, a_src, b_src, row64, k0);
   };
-
-  // Fragment reads: lane l reads row (l&15) of a 16-row block at logical chunk 4kk + (l>>4).
-  const int frow = lane & 15;
-  const int foff0 = frow * 128 + (((lane >> 4) ^ (frow >> 1)) << 4);  // kk = 0; kk = 1: ^ 64
-  const int a_off = wm * 128 * 128 + foff0;
-  const int b_off = kTileBytes + wn * 64 * 128 + foff0;
-
   f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  tile_zero(acc);
 
   const int nt = K / TK;
   stage(0, 0);
@@ -100,11 +63,11 @@ __global__ __launch_bounds__(512) void k_gemm_nt256(const __bf16* __restrict__ A
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           bfr[kk][j] =
-              *reinterpret_cast<const bf16x8*>(sb + ((b_off + j * 16 * 128) ^ (kk << 6)));
+              *reinterpret_cast<const bf16x8*>(sb + ((c.b_off + j * 16 * 128) ^ (kk << 6)));
 #pragma unroll
         for (int i = 0; i < 8; ++i)
           af[kk][i] =
-              *reinterpret_cast<const bf16x8*>(sb + ((a_off + i * 16 * 128) ^ (kk << 6)));
+              *reinterpret_cast<const bf16x8*>(sb + ((c.a_off + i * 16 * 128) ^ (kk << 6)));
       }
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -120,17 +83,7 @@ __global__ __launch_bounds__(512) void k_gemm_nt256(const __bf16* __restrict__ A
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
-
-  // Epilogue: C/D map of 16x16x32: col = l&15, row = 4(l>>4) + reg.
-  const int crow = tm * TM + wm * 128 + 4 * (lane >> 4);
-  const int ccol = tn * TN + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] = (__bf16)acc[i][j][r];
+  tile_store<false>(c, C, N, tm, tn, acc, 0);
 }
 
 // V5 — V1's geometry with a local-read prefetch across the barrier. The second k-step's MFMAs
@@ -141,8 +94,14 @@ __global__ __launch_bounds__(512) void k_gemm_nt256(const __bf16* __restrict__ A
 //
 // kTraced: the attributed burn-in's form of the same schedule. The tile comes from the map
 // rotated by tr.r, thread 0 stores the block's CU id under the tile, and a block on the injected
-// CU flips element (0, 0) of its tile on the way out (trace_block, gm_gemm_shared.h). Nothing
+// CU flips element (0, 0) of its tile on the way out (tile_pick, gm_gemm_shared.h). Nothing
 // else differs: operands, order of summation and epilogue are the plain form's.
+//
+// This body, the one the burn-in and gemm_tflops time, spells the tile frame's coordinates,
+// stage, zeroing and epilogue out (the same text as TileLane, tile_stage, tile_zero and
+// tile_store; change them together). Written on those pieces it computes the same bits, but the
+// compiler orders its address arithmetic and epilogue stores differently, and it measured 0.3 %
+// (8192³) to 1.2 % (4096³) slower: profiles/burnin_attr/README.md.
 template <bool kTraced>
 __device__ __forceinline__ void gemm_nt256p_block(const __bf16* __restrict__ A,
                                                   const __bf16* __restrict__ Bt,
@@ -154,13 +113,7 @@ __device__ __forceinline__ void gemm_nt256p_block(const __bf16* __restrict__ A,
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   int tm, tn;
-  uint32_t flip = 0;
-  if constexpr (kTraced) {
-    gemm_tile_of(M, N, tm, tn, tr.r);
-    flip = trace_block(tr, tm * (N / TN) + tn);
-  } else {
-    gemm_tile_of(M, N, tm, tn);
-  }
+  const uint32_t flip = tile_pick<kTraced>(M, N, tr, tm, tn);
   const int srow = 8 * wave + (lane >> 3);
   const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
   const __bf16* a_src = A + (size_t)(tm * TM + srow) * K + schunk * 8;
@@ -280,6 +233,33 @@ int launch_fill_bf16(void* dst, size_t n, uint32_t seed, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+// The one launch of the traced kernel; the arguments were checked.
+int launch_gemm_nt_traced(const void* A, const void* Bt, void* C, int M, int N, int K,
+                          const GemmTrace& tr, hipStream_t stream) {
+  using namespace g256;
+  hipLaunchKernelGGL(k_gemm_nt256p_traced, dim3((M / TM) * (N / TN)), dim3(kThreads), 0, stream,
+                     (const __bf16*)A, (const __bf16*)Bt, (__bf16*)C, M, N, K, tr);
+  return (int)hipGetLastError();
+}
+
+// The bf16 burn-in's operands (gm_gemm_shared.h, "the burn-in driver"); bf16 has no format code.
+struct BurnInBf16 {
+  DevBuf da, db;
+  explicit BurnInBf16(int) {}
+  static bool shape_ok(int, int n) { return n > 0 && n % g256::TM == 0; }
+  int fill(int n) {
+    const size_t elems = (size_t)n * n;
+    GM_CHECK(da.alloc(elems * 2));
+    GM_CHECK(db.alloc(elems * 2));
+    const int e = launch_fill_bf16(da.p, elems, 0x5151u, nullptr);
+    return e ? e : launch_fill_bf16(db.p, elems, 0xa3a3u, nullptr);
+  }
+  int gemm(void* c, int n) const { return gm_probe_gemm_nt(da.p, db.p, c, n, n, n, nullptr); }
+  int gemm_traced(void* c, int n, const GemmTrace& tr) const {
+    return launch_gemm_nt_traced(da.p, db.p, c, n, n, n, tr, nullptr);
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -367,25 +347,8 @@ int gm_probe_burn_in(int dev, int n, double seconds, double* tflops, uint64_t* m
 int gm_probe_burn_in_flip(int dev, int n, double seconds, int n_flips,
                           const uint64_t* flip_elems, const uint16_t* flip_masks,
                           double* tflops, uint64_t* mismatches, int* iters) {
-  using namespace g256;
-  *tflops = 0;
-  *mismatches = 0;
-  *iters = 0;
-  if (n <= 0 || n % TM || seconds <= 0) return (int)hipErrorInvalidValue;
-  const size_t elems = (size_t)n * n;
-  if (!burn_in_flips_ok(elems, n_flips, flip_elems, flip_masks)) return (int)hipErrorInvalidValue;
-  DeviceGuard g(dev);
-  if (!g.ok) return (int)hipErrorInvalidDevice;
-  DevBuf da, db;
-  GM_CHECK(da.alloc(elems * 2));
-  GM_CHECK(db.alloc(elems * 2));
-  int e = launch_fill_bf16(da.p, elems, 0x5151u, nullptr);
-  if (!e) e = launch_fill_bf16(db.p, elems, 0xa3a3u, nullptr);
-  if (e) return e;
-  return burn_in_loop(
-      n, seconds, n_flips, flip_elems, flip_masks,
-      [&](void* c) { return gm_probe_gemm_nt(da.p, db.p, c, n, n, n, nullptr); }, tflops,
-      mismatches, iters);
+  return burn_in_run<BurnInBf16>(0, dev, n, seconds, n_flips, flip_elems, flip_masks, tflops,
+                                 mismatches, iters);
 }
 
 // ------------------------------------------------------------------ attributed burn-in
@@ -425,20 +388,14 @@ int gm_probe_gemm_nt_traced(const void* A, const void* Bt, void* C, int M, int N
   if (r < 0 || r >= grid || !cu_of_tile || ((uintptr_t)cu_of_tile & 3) ||
       !burn_in_inject_ok(inject) || (inject && inject->first))
     return (int)hipErrorInvalidValue;
-  const GemmTrace tr{r, cu_of_tile, nullptr, inject ? inject->id : 0,
-                     inject ? inject->mask : 0};
-  hipLaunchKernelGGL(k_gemm_nt256p_traced, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
-                     (const __bf16*)A, (const __bf16*)Bt, (__bf16*)C, M, N, K, tr);
-  return (int)hipGetLastError();
+  return launch_gemm_nt_traced(
+      A, Bt, C, M, N, K,
+      GemmTrace{r, cu_of_tile, nullptr, inject ? inject->id : 0, inject ? inject->mask : 0},
+      (hipStream_t)stream);
 }
 
 int gm_probe_gemm_nt_traced_info(int* num_regs, int* scratch_bytes) {
-  if (!num_regs || !scratch_bytes) return (int)hipErrorInvalidValue;
-  hipFuncAttributes attr;
-  GM_CHECK(hipFuncGetAttributes(&attr, (const void*)k_gemm_nt256p_traced));
-  *num_regs = attr.numRegs;
-  *scratch_bytes = (int)attr.localSizeBytes;
-  return 0;
+  return kernel_regs((const void*)k_gemm_nt256p_traced, num_regs, scratch_bytes);
 }
 
 int gm_probe_count_diff_tiles(const void* a, const void* b, int n, const uint32_t* cu,
@@ -463,33 +420,9 @@ int gm_probe_burn_in_attr(int dev, int n, double seconds, int n_flips,
                           const gm_burnin_inject_t* inject, double* tflops,
                           uint64_t* mismatches, int* iters, gm_burnin_attr_t* attr,
                           gm_burnin_blamed_t* blamed, int blamed_cap) {
-  using namespace g256;
-  *tflops = 0;
-  *mismatches = 0;
-  *iters = 0;
-  if (!attr || blamed_cap < 0 || (blamed_cap > 0 && !blamed)) return (int)hipErrorInvalidValue;
-  *attr = gm_burnin_attr_t{};
-  if (n <= 0 || n % TM || seconds <= 0 || !burn_in_inject_ok(inject))
-    return (int)hipErrorInvalidValue;
-  const size_t elems = (size_t)n * n;
-  if (!burn_in_flips_ok(elems, n_flips, flip_elems, flip_masks)) return (int)hipErrorInvalidValue;
-  DeviceGuard g(dev);
-  if (!g.ok) return (int)hipErrorInvalidDevice;
-  DevBuf da, db;
-  GM_CHECK(da.alloc(elems * 2));
-  GM_CHECK(db.alloc(elems * 2));
-  int e = launch_fill_bf16(da.p, elems, 0x5151u, nullptr);
-  if (!e) e = launch_fill_bf16(db.p, elems, 0xa3a3u, nullptr);
-  if (e) return e;
-  return burn_in_attr_loop(
-      n, seconds, n_flips, flip_elems, flip_masks, inject,
-      [&](void* c, const GemmTrace& tr) {
-        hipLaunchKernelGGL(k_gemm_nt256p_traced, dim3((n / TM) * (n / TN)), dim3(kThreads), 0,
-                           nullptr, (const __bf16*)da.p, (const __bf16*)db.p, (__bf16*)c, n, n, n,
-                           tr);
-        return (int)hipGetLastError();
-      },
-      tflops, mismatches, iters, attr, blamed, blamed_cap);
+  const BurnInAttr at{inject, attr, blamed, blamed_cap};
+  return burn_in_run<BurnInBf16>(0, dev, n, seconds, n_flips, flip_elems, flip_masks, tflops,
+                                 mismatches, iters, &at);
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // gm_gemm_shared.h — what the two burn-in GEMMs (gm_gemm.hip: bf16, gm_mxgemm.hip: block-scaled
-// fp8 / fp4) share: the XCD-aware block → tile map, the compare kernel and the bit-exact burn-in
-// loop with its flip control; and for the attributed burn-in the traced blocks' bookkeeping, the
-// per-tile compare and the traced loop. In an anonymous namespace, like gm_probe_common.h: each
-// translation unit gets its own copy.
+// fp8 / fp4) share: the 256² tile frame of their kernels (geometry, per-thread coordinates,
+// operand stage, tile pick, epilogue; the schedules stay with the kernels), the compare kernels
+// and the burn-in driver: one front for the plain and the attributed entry points of either
+// format, its two loops, their flip control and timed batches. In an anonymous namespace, like
+// gm_probe_common.h: each translation unit gets its own copy.
 #pragma once
 
 #include <stddef.h>
@@ -12,14 +13,6 @@
 #include "gm_where.h"
 
 namespace {
-
-// XCD-aware block → output tile (gm_gemm_tile_map, gm_burnin_attr.h) of this block. r = 0, the
-// default and a constant in the plain kernels, folds away; the traced kernels pass the
-// iteration's rotation, 0 <= r < gridDim.x.
-template <int TM, int TN, int kGroupM>
-__device__ __forceinline__ void gemm_tile_of(int M, int N, int& tm, int& tn, int r = 0) {
-  gm_gemm_tile_map<TM, TN, kGroupM>((int)blockIdx.x, (int)gridDim.x, M, N, r, tm, tn);
-}
 
 // What a traced GEMM takes besides its operands: the rotation, where each block stores the id
 // of the CU it ran on, and the injection (mask 0: none). The injected id is inj_id or, where
@@ -49,6 +42,113 @@ __device__ __forceinline__ __bf16 bf16_flipped(float v, uint32_t flip) {
   const __bf16 b = (__bf16)v;
   const uint16_t bits = (uint16_t)(__builtin_bit_cast(uint16_t, b) ^ flip);
   return __builtin_bit_cast(__bf16, bits);
+}
+
+// ------------------------------------------------------------------ the 256² tile frame
+// The geometry all three kernel bodies have (design notes: gm_gemm.hip): a 256×256 output tile,
+// 512 threads = 8 waves as 2(M)×4(N), each wave 128×64 as 8×4 16x16 accumulators; a K-tile is 128
+// bytes of every row (64 bf16, 128 fp8, 256 fp4), so one operand's stage is 32 KiB whatever the
+// format, and the byte layout below is the same for all of them.
+namespace tile256 {
+constexpr int TM = 256, TN = 256, kRowBytes = 128, kThreads = 512, kGroupM = 8;
+constexpr int kTileBytes = TM * kRowBytes;    // 32 KiB: one operand, one stage
+constexpr int kStageBytes = 2 * kTileBytes;   // A + Bt
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(1))) void gbl_void;
+}  // namespace tile256
+
+// A thread's coordinates in the tile, computed once. The XOR swizzle of the 16-B chunk index
+// with (row>>1)&7 removes the bank conflicts of the 16-row ds_read_b128 fragment reads; it is
+// applied to the per-lane GLOBAL source address (schunk) and to the LDS read address (foff0),
+// and the two are only ever changed together, here.
+struct TileLane {
+  int lane, wave, wm, wn;  // wave (uniform) = 4 wm + wn
+  // Staging: wave w moves 1 KiB chunks c = w + 8i (i = 0..3) of each operand's 256-row tile.
+  // Lane l writes LDS byte c*1024 + l*16 = row 8c + (l>>3), slot l&7, which holds logical
+  // 16-B chunk (l&7) ^ ((row>>1)&7). (row>>1)&7 is the same for all i (rows differ by 64).
+  int srow, schunk;
+  // Fragment reads: lane l reads row frow = l&15 of a 16-row block at logical chunk l>>4 of the
+  // first 64 bytes (foff0; the second 64: ^ 64); a_off / b_off: that in this wave's rows of the
+  // A / Bt half of a stage, 16-row block i a further i * 2048.
+  int frow, foff0, a_off, b_off;
+};
+__device__ __forceinline__ TileLane tile_lane() {
+  using namespace tile256;
+  TileLane c;
+  const int tid = threadIdx.x;
+  c.lane = tid & 63;
+  c.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  c.wm = c.wave >> 2, c.wn = c.wave & 3;
+  c.srow = 8 * c.wave + (c.lane >> 3);
+  c.schunk = (c.lane & 7) ^ ((c.srow >> 1) & 7);
+  c.frow = c.lane & 15;
+  c.foff0 = c.frow * 128 + (((c.lane >> 4) ^ (c.frow >> 1)) << 4);
+  c.a_off = c.wm * 128 * 128 + c.foff0;
+  c.b_off = kTileBytes + c.wn * 64 * 128 + c.foff0;
+  return c;
+}
+
+// This thread's 16 staged bytes of K-tile 0, in row row0 + srow of an operand whose rows are
+// `row` elements of T apart.
+template <class T>
+__device__ __forceinline__ const T* tile_src(const TileLane& c, const T* op, int row0, size_t row) {
+  return op + (size_t)(row0 + c.srow) * row + c.schunk * (16 / (int)sizeof(T));
+}
+
+// The operand stage: HBM→LDS with global_load_lds_dwordx4 (no VGPR round trip), 2 × 4 of them
+// per thread, into the stage at `stage`. a_src / b_src from tile_src; row64, the stride of 64
+// rows, and k0, the K-tile's offset, in elements of T.
+template <class T, class K0>
+__device__ __forceinline__ void tile_stage(const TileLane& c, char* stage, const T* a_src,
+                                           const T* b_src, size_t row64, K0 k0) {
+  using namespace tile256;
+  char* base = stage + c.wave * 1024;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    __builtin_amdgcn_global_load_lds((gbl_void*)(a_src + i * row64 + k0),
+                                     (lds_void*)(base + i * 8192), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_void*)(b_src + i * row64 + k0),
+                                     (lds_void*)(base + kTileBytes + i * 8192), 16, 0, 0);
+  }
+}
+
+__device__ __forceinline__ void tile_zero(f32x4 (&acc)[8][4]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// The block's output tile: the XCD-aware map (gm_gemm_tile_map, gm_burnin_attr.h), in the plain
+// kernels at rotation 0, a constant that folds away. kTraced, the attributed burn-in's form: at
+// the iteration's rotation tr.r, and the block books itself (trace_block). Returns the flip the
+// epilogue takes.
+template <bool kTraced>
+__device__ __forceinline__ uint32_t tile_pick(int M, int N, const GemmTrace& tr, int& tm, int& tn) {
+  using namespace tile256;
+  gm_gemm_tile_map<TM, TN, kGroupM>((int)blockIdx.x, (int)gridDim.x, M, N, kTraced ? tr.r : 0, tm,
+                                    tn);
+  if constexpr (kTraced) return trace_block(tr, tm * (N / TN) + tn);
+  return 0;
+}
+
+// Epilogue: the C/D map of the 16x16 MFMA shapes: col = l&15, row = 4(l>>4) + reg. kTraced:
+// element (0, 0) of the tile leaves with `flip` XORed into its bits.
+template <bool kTraced>
+__device__ __forceinline__ void tile_store(const TileLane& c, __bf16* __restrict__ C, int N, int tm,
+                                           int tn, const f32x4 (&acc)[8][4], uint32_t flip) {
+  using namespace tile256;
+  const int crow = tm * TM + c.wm * 128 + 4 * (c.lane >> 4);
+  const int ccol = tn * TN + c.wn * 64 + (c.lane & 15);
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] =
+            kTraced && i == 0 && j == 0 && r == 0 ? bf16_flipped(acc[0][0][0], flip)
+                                                  : (__bf16)acc[i][j][r];
 }
 
 // Number of 16-B words that differ between a and b: one ballot + popcount per wave, one
@@ -86,61 +186,96 @@ inline bool burn_in_flips_ok(size_t elems, int n_flips, const uint64_t* flip_ele
   return true;
 }
 
-// The burn-in proper, on the current device with the operands already filled: gemm(c) launches
-// one n³ GEMM into the n × n bf16 buffer c on the null stream and returns a HIP error code. The
-// first result is the reference; the flips are applied to it; every later result is compared with
-// it. *tflops counts 2 n³ per GEMM over the wall time, compare kernels included.
-template <class Gemm>
-int burn_in_loop(int n, double seconds, int n_flips, const uint64_t* flip_elems,
-                 const uint16_t* flip_masks, Gemm gemm, double* tflops, uint64_t* mismatches,
-                 int* iters) {
+// numRegs and localSizeBytes of a kernel from hipFuncGetAttributes on the current device.
+inline int kernel_regs(const void* kernel, int* num_regs, int* scratch_bytes) {
+  if (!num_regs || !scratch_bytes) return (int)hipErrorInvalidValue;
+  hipFuncAttributes attr;
+  GM_CHECK(hipFuncGetAttributes(&attr, kernel));
+  *num_regs = attr.numRegs;
+  *scratch_bytes = (int)attr.localSizeBytes;
+  return 0;
+}
+
+// ------------------------------------------------------------------ the burn-in driver
+// A format's side of a burn-in is one small operand object, made from the format's code:
+//   static bool shape_ok(int fmt, int n)  the format takes n × n × n
+//   int fill(int n)                      allocates the operands and fills them (seeds 0x5151 and
+//                                         0xa3a3) on the current device
+//   int gemm(void* c, int n) const        launches one n³ GEMM into the n × n bf16 buffer c on
+//   int gemm_traced(void* c, int n, const GemmTrace&) const      the null stream, plain / traced
+// all but the first returning a HIP error code. BurnInBf16 (gm_gemm.hip) and BurnInMx
+// (gm_mxgemm.hip) are the two.
+
+// The negative control: corrupt the finished reference, through the host like the memtest's flip.
+// The blocking copies on the null stream wait for the GEMM before them.
+inline int burn_in_flip_reference(void* ref, int n_flips, const uint64_t* flip_elems,
+                                  const uint16_t* flip_masks) {
+  for (int i = 0; i < n_flips; ++i) {
+    uint16_t* at = (uint16_t*)ref + flip_elems[i];
+    uint16_t v = 0;
+    GM_CHECK(hipMemcpy(&v, at, sizeof(v), hipMemcpyDeviceToHost));
+    v ^= flip_masks[i];
+    GM_CHECK(hipMemcpy(at, &v, sizeof(v), hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
+// The timed part of a burn-in: step(i), i = 1, 2, ..., launches iteration i's GEMM and compare on
+// the null stream, in order, so the next GEMM overwrites a result only after the compare has
+// read it. Batches of 8 steps with a synchronisation after each, until `seconds` have passed.
+// *done: the steps launched; *ms: their time between two events.
+template <class Step>
+int burn_in_timed(double seconds, Step step, int* done, float* ms) {
+  Events ev;
+  GM_CHECK(ev.create());
+  GM_CHECK(hipEventRecord(ev.e0, nullptr));
+  const double t0 = now_s();
+  int e = 0;
+  while (!e) {
+    for (int i = 0; i < 8 && !e; ++i) e = step(++*done);
+    if (!e) e = (int)hipDeviceSynchronize();
+    if (now_s() - t0 >= seconds) break;
+  }
+  if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
+  if (!e) e = (int)hipEventSynchronize(ev.e1);
+  if (!e) e = elapsed_ms(ev.e0, ev.e1, ms);
+  return e;
+}
+
+// 2 n³ per GEMM over the wall time. The compare kernels are included; they move 2 × n² × 2 B per
+// GEMM (about 2 % of a bf16 GEMM's time at 8192³, more of the shorter MX ones: profiles/mxgemm/).
+inline double burn_in_tflops(int n, int done, float ms) {
+  return ms > 0 ? 2.0 * n * (double)n * n * done / (ms * 1e-3) / 1e12 : 0;
+}
+
+// The plain burn-in, on the current device with the operands filled. The first result is the
+// reference; the flips are applied to it; every later result is compared with it bit for bit: the
+// kernel is deterministic (fixed reduction order, no atomics), so any difference is a hardware
+// fault.
+template <class Operands>
+int burn_in_loop(const Operands& ops, int n, double seconds, int n_flips,
+                 const uint64_t* flip_elems, const uint16_t* flip_masks, double* tflops,
+                 uint64_t* mismatches, int* iters) {
   const size_t elems = (size_t)n * n;
   DevBuf dref, dc, dcount;
   GM_CHECK(dref.alloc(elems * 2));
   GM_CHECK(dc.alloc(elems * 2));
   GM_CHECK(dcount.alloc(sizeof(unsigned long long)));
   GM_CHECK(hipMemset(dcount.p, 0, sizeof(unsigned long long)));
-  int e = gemm(dref.p);  // the reference result
-  if (e) return e;
-  // Negative control: corrupt the finished reference, through the host like the memtest's flip.
-  // The blocking copies on the null stream wait for the GEMM; the loop below is untouched.
-  for (int i = 0; i < n_flips; ++i) {
-    uint16_t* at = (uint16_t*)dref.p + flip_elems[i];
-    uint16_t v = 0;
-    GM_CHECK(hipMemcpy(&v, at, sizeof(v), hipMemcpyDeviceToHost));
-    v ^= flip_masks[i];
-    GM_CHECK(hipMemcpy(at, &v, sizeof(v), hipMemcpyHostToDevice));
-  }
-  Events ev;
-  GM_CHECK(ev.create());
-  GM_CHECK(hipEventRecord(ev.e0, nullptr));
-  const double t0 = now_s();
-  const size_t vec = elems / 8;  // 16-B compares
+  if (int e = ops.gemm(dref.p, n)) return e;  // the reference result
+  if (int e = burn_in_flip_reference(dref.p, n_flips, flip_elems, flip_masks)) return e;
   int done = 0;
-  // Batches of 8 GEMMs, each result compared bit-for-bit with the first one: the kernel is
-  // deterministic (fixed reduction order, no atomics), so any difference is a hardware fault.
-  while (!e) {
-    for (int i = 0; i < 8 && !e; ++i) {
-      e = gemm(dc.p);
-      if (!e) e = launch_count_diff(dc.p, dref.p, vec, dcount.p, nullptr);
-      ++done;
-    }
-    if (!e) e = (int)hipDeviceSynchronize();
-    const double el = now_s() - t0;
-    if (el >= seconds) break;
-  }
-  if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
-  if (!e) e = (int)hipEventSynchronize(ev.e1);
   float ms = 0;
-  if (!e) e = elapsed_ms(ev.e0, ev.e1, &ms);
+  const auto step = [&](int) {
+    const int rc = ops.gemm(dc.p, n);
+    return rc ? rc : launch_count_diff(dc.p, dref.p, elems / 8, dcount.p, nullptr);  // 16-B words
+  };
+  if (int e = burn_in_timed(seconds, step, &done, &ms)) return e;
   unsigned long long bad = 0;
-  if (!e) e = (int)hipMemcpy(&bad, dcount.p, sizeof(bad), hipMemcpyDeviceToHost);
-  if (e) return e;
+  GM_CHECK(hipMemcpy(&bad, dcount.p, sizeof(bad), hipMemcpyDeviceToHost));
   *iters = done;
   *mismatches = bad;
-  // compare kernels are included in the wall time; they move 2 × n² × 2 B per GEMM (about 2 %
-  // of a bf16 GEMM's time at 8192³, more of the shorter MX ones: profiles/mxgemm/)
-  if (ms > 0) *tflops = 2.0 * n * (double)n * n * done / (ms * 1e-3) / 1e12;
+  *tflops = burn_in_tflops(n, done, ms);
   return 0;
 }
 
@@ -220,12 +355,21 @@ inline bool burn_in_inject_ok(const gm_burnin_inject_t* in) {
   return !in || (in->mask >= 1 && in->mask <= 0xFFFF && (in->first || in->id < GM_CUSCAN_IDS));
 }
 
-// burn_in_loop's sibling: gemm(c, trace) launches one traced n³ GEMM on the null stream.
-template <class Gemm>
-int burn_in_attr_loop(int n, double seconds, int n_flips, const uint64_t* flip_elems,
-                      const uint16_t* flip_masks, const gm_burnin_inject_t* inject, Gemm gemm,
-                      double* tflops, uint64_t* mismatches, int* iters, gm_burnin_attr_t* attr,
-                      gm_burnin_blamed_t* blamed, int blamed_cap) {
+// What an attributed burn-in takes and gives besides a plain one's arguments.
+struct BurnInAttr {
+  const gm_burnin_inject_t* inject;
+  gm_burnin_attr_t* attr;
+  gm_burnin_blamed_t* blamed;
+  int blamed_cap;
+};
+
+// burn_in_loop's sibling, on the traced GEMM: the tiles rotate from one iteration to the next.
+template <class Operands>
+int burn_in_attr_loop(const Operands& ops, int n, double seconds, int n_flips,
+                      const uint64_t* flip_elems, const uint16_t* flip_masks, const BurnInAttr& at,
+                      double* tflops, uint64_t* mismatches, int* iters) {
+  const gm_burnin_inject_t* inject = at.inject;
+  gm_burnin_attr_t* attr = at.attr;
   const size_t elems = (size_t)n * n;
   const int tiles = (n / kBurninTile) * (n / kBurninTile), grid = tiles;
   const int step = gm_burnin_step(grid);
@@ -262,7 +406,7 @@ int burn_in_attr_loop(int n, double seconds, int n_flips, const uint64_t* flip_e
     return launch_count_diff_tiles(c, dref.p, n, iteration, maps, dst.p, nullptr);
   };
   GemmTrace tr{0, (uint32_t*)dwarm.p, nullptr, 0, 0};
-  int e = gemm(dref.p, tr);
+  int e = ops.gemm_traced(dref.p, n, tr);
   if (!e) e = compare(dref.p, dwarm.p, dwarm.p, 0);
   if (e) return e;
   if (inject) {
@@ -272,39 +416,19 @@ int burn_in_attr_loop(int n, double seconds, int n_flips, const uint64_t* flip_e
   }
   // The reference result and its CU map, then the same compare: it books the reference's CUs.
   tr.cu_of_tile = (uint32_t*)dref_cu.p;
-  e = gemm(dref.p, tr);
+  e = ops.gemm_traced(dref.p, n, tr);
   if (!e) e = compare(dref.p, dref_cu.p, dref_cu.p, 0);
   if (e) return e;
-  for (int i = 0; i < n_flips; ++i) {  // as in burn_in_loop
-    uint16_t* at = (uint16_t*)dref.p + flip_elems[i];
-    uint16_t v = 0;
-    GM_CHECK(hipMemcpy(&v, at, sizeof(v), hipMemcpyDeviceToHost));
-    v ^= flip_masks[i];
-    GM_CHECK(hipMemcpy(at, &v, sizeof(v), hipMemcpyHostToDevice));
-  }
+  if ((e = burn_in_flip_reference(dref.p, n_flips, flip_elems, flip_masks))) return e;
   tr.cu_of_tile = (uint32_t*)dcu.p;
-  Events ev;
-  GM_CHECK(ev.create());
-  GM_CHECK(hipEventRecord(ev.e0, nullptr));
-  const double t0 = now_s();
   int done = 0;
-  // Batches of 8 as in burn_in_loop; GEMM and compare in order on the one stream, so the next
-  // GEMM overwrites the result and the CU map only after the compare has read them.
-  while (!e) {
-    for (int i = 0; i < 8 && !e; ++i) {
-      tr.r = gm_burnin_rotation(grid, step, done + 1);
-      e = gemm(dc.p, tr);
-      if (!e) e = compare(dc.p, dcu.p, dref_cu.p, (uint32_t)(done + 1));
-      ++done;
-    }
-    if (!e) e = (int)hipDeviceSynchronize();
-    if (now_s() - t0 >= seconds) break;
-  }
-  if (!e) e = (int)hipEventRecord(ev.e1, nullptr);
-  if (!e) e = (int)hipEventSynchronize(ev.e1);
   float ms = 0;
-  if (!e) e = elapsed_ms(ev.e0, ev.e1, &ms);
-  if (e) return e;
+  const auto iteration = [&](int i) {
+    tr.r = gm_burnin_rotation(grid, step, i);
+    const int rc = ops.gemm_traced(dc.p, n, tr);
+    return rc ? rc : compare(dc.p, dcu.p, dref_cu.p, (uint32_t)i);
+  };
+  if ((e = burn_in_timed(seconds, iteration, &done, &ms))) return e;
 
   std::vector<unsigned char> raw(sizeof(AttrState));
   std::vector<uint32_t> exon(tiles), moved(tiles), seen(GM_CUSCAN_IDS);
@@ -329,11 +453,38 @@ int burn_in_attr_loop(int n, double seconds, int n_flips, const uint64_t* flip_e
   attr->rotations = (uint32_t)(done < grid ? done : grid);  // step is coprime to the grid
   attr->first_id = first;
   attr->inject_id = !inject ? GM_CUSCAN_ANY : inject->first ? first : inject->id;
-  gm_burnin_store_blame(blame, st->log, attr, blamed, blamed_cap);
+  gm_burnin_store_blame(blame, st->log, attr, at.blamed, at.blamed_cap);
   *iters = done;
   *mismatches = st->total;
-  if (ms > 0) *tflops = 2.0 * n * (double)n * n * done / (ms * 1e-3) / 1e12;
+  *tflops = burn_in_tflops(n, done, ms);
   return 0;
+}
+
+// The front of the four burn-in entry points: the plain burn-in, or with `at` the attributed one.
+// The outputs are zeroed before any refusal, and every refusal comes before the device is chosen.
+template <class Operands>
+int burn_in_run(int fmt, int dev, int n, double seconds, int n_flips,
+                const uint64_t* flip_elems, const uint16_t* flip_masks, double* tflops,
+                uint64_t* mismatches, int* iters, const BurnInAttr* at = nullptr) {
+  *tflops = 0;
+  *mismatches = 0;
+  *iters = 0;
+  if (at) {
+    if (!at->attr || at->blamed_cap < 0 || (at->blamed_cap > 0 && !at->blamed))
+      return (int)hipErrorInvalidValue;
+    *at->attr = gm_burnin_attr_t{};
+  }
+  if (!Operands::shape_ok(fmt, n) || seconds <= 0 || (at && !burn_in_inject_ok(at->inject)) ||
+      !burn_in_flips_ok((size_t)n * n, n_flips, flip_elems, flip_masks))
+    return (int)hipErrorInvalidValue;
+  DeviceGuard g(dev);
+  if (!g.ok) return (int)hipErrorInvalidDevice;
+  Operands ops(fmt);  // after the guard: its buffers go before the device is restored
+  if (int e = ops.fill(n)) return e;
+  if (at)
+    return burn_in_attr_loop(ops, n, seconds, n_flips, flip_elems, flip_masks, *at, tflops,
+                             mismatches, iters);
+  return burn_in_loop(ops, n, seconds, n_flips, flip_elems, flip_masks, tflops, mismatches, iters);
 }
 
 }  // namespace

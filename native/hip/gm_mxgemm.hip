@@ -11,11 +11,12 @@
 namespace {
 
 // ------------------------------------------------------------------ MX GEMM, 256² tile
-// The geometry of the bf16 kernel (gm_gemm.hip, k_gemm_nt256): 256×256 output tile, 512 threads
-// = 8 waves as 2(M)×4(N), each wave 128×64 as 8×4 16x16 accumulators; operands HBM→LDS with
-// global_load_lds_dwordx4, two stages, the same XOR swizzle of the 16-B chunk index with
-// (row>>1)&7; the same block → tile map. A K-tile is 128 bytes of every row, as there, so the
-// byte layout carries over: 128 elements of fp8 (one MFMA per accumulator), 256 of fp4 (two).
+// On the tile frame of gm_gemm_shared.h, like the bf16 kernels (gm_gemm.hip): 256×256 output
+// tile, 512 threads = 8 waves as 2(M)×4(N), each wave 128×64 as 8×4 16x16 accumulators; operands
+// HBM→LDS with global_load_lds_dwordx4, two stages, the XOR swizzle of the 16-B chunk index with
+// (row>>1)&7; the block → tile map. A K-tile is 128 bytes of every row, so the byte layout is
+// the bf16 kernels': 128 elements of fp8 (one MFMA per accumulator), 256 of fp4 (two). Here are
+// the schedule, the fragments and the scales.
 //
 // Lane maps of v_mfma_scale_f32_16x16x128_f8f6f4 (lane l holds row / column l & 15, g = l >> 4):
 //   fp8: bytes 0-15 are k = 16 g + j, bytes 16-31 are k = 64 + 16 g + (j - 16): logical chunks g
@@ -29,15 +30,11 @@ namespace {
 // per thread and step (thread t: operand t >> 8, row t & 255) into 4 KiB per stage behind the
 // operand stages; a lane reads its byte with ds_read_u8 right before the MFMA that uses it.
 namespace mx256 {
-constexpr int TM = 256, TN = 256, kRowBytes = 128, kThreads = 512, kGroupM = 8;
-constexpr int kTileBytes = TM * kRowBytes;     // 32 KiB: one operand, one stage
-constexpr int kStageBytes = 2 * kTileBytes;    // A + Bt
+using namespace tile256;                       // the geometry itself: gm_gemm_shared.h
 constexpr int kScaleStep = (TM + TN) * 4;      // 2 KiB: every row's 4 scale bytes of one step
 constexpr int kScaleStage = 2 * kScaleStep;    // fp4 has two steps per K-tile
 constexpr int kScaleBase = 2 * kStageBytes;    // 128 KiB of operands first
 constexpr int kLdsBytes = kScaleBase + 2 * kScaleStage;  // 136 KiB of the 160 KiB LDS
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) void gbl_void;
 }  // namespace mx256
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -70,61 +67,34 @@ __device__ __forceinline__ void mxgemm_nt_block(const uint8_t* __restrict__ A,
   using namespace mx256;
   constexpr int kSteps = FMT == GM_MX_FP4 ? 2 : 1;  // MFMAs of K = 128 per accumulator and K-tile
   __shared__ __attribute__((aligned(1024))) char lds[kLdsBytes];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
+  const int tid = threadIdx.x;
   int tm, tn;
-  uint32_t flip = 0;
-  if constexpr (kTraced) {
-    gemm_tile_of<TM, TN, kGroupM>(M, N, tm, tn, tr.r);
-    flip = trace_block(tr, tm * (N / TN) + tn);
-  } else {
-    gemm_tile_of<TM, TN, kGroupM>(M, N, tm, tn);
-  }
+  const uint32_t flip = tile_pick<kTraced>(M, N, tr, tm, tn);
+  const TileLane c = tile_lane();
 
-  // Operand staging, as in k_gemm_nt256: wave w moves 1 KiB chunks c = w + 8i of each operand's
-  // 256-row tile; lane l writes row 8c + (l>>3), slot l&7 = logical chunk (l&7) ^ ((row>>1)&7).
   const size_t row_bytes = gm_mx_row_bytes(FMT, (size_t)K), srow_bytes = (size_t)K / GM_MX_BLOCK;
-  const int srow = 8 * wave + (lane >> 3);
-  const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
-  const uint8_t* a_src = A + (size_t)(tm * TM + srow) * row_bytes + schunk * 16;
-  const uint8_t* b_src = Bt + (size_t)(tn * TN + srow) * row_bytes + schunk * 16;
-  const size_t row64 = 64 * row_bytes;
+  const uint8_t* a_src = tile_src(c, A, tm * TM, row_bytes);
+  const uint8_t* b_src = tile_src(c, Bt, tn * TN, row_bytes);
   // Scale staging: waves 0-3 move A's rows 64 w + l, waves 4-7 Bt's, 4 bytes per step.
-  const uint8_t* s_src = wave < 4 ? sA + (size_t)(tm * TM + tid) * srow_bytes
-                                  : sB + (size_t)(tn * TN + tid - TM) * srow_bytes;
+  const uint8_t* s_src = c.wave < 4 ? sA + (size_t)(tm * TM + tid) * srow_bytes
+                                    : sB + (size_t)(tn * TN + tid - TM) * srow_bytes;
 
   auto stage = [&](int buf, int t) {
-    char* base = lds + buf * kStageBytes + wave * 1024;
-    const size_t k0 = (size_t)t * kRowBytes;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      __builtin_amdgcn_global_load_lds((gbl_void*)(a_src + i * row64 + k0),
-                                       (lds_void*)(base + i * 8192), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gbl_void*)(b_src + i * row64 + k0),
-                                       (lds_void*)(base + kTileBytes + i * 8192), 16, 0, 0);
-    }
-    char* sbase = lds + kScaleBase + buf * kScaleStage + wave * 256;
+    tile_stage(c, lds + buf * kStageBytes, a_src, b_src, 64 * row_bytes, (size_t)t * kRowBytes);
+    char* sbase = lds + kScaleBase + buf * kScaleStage + c.wave * 256;
 #pragma unroll
     for (int kk = 0; kk < kSteps; ++kk)
       __builtin_amdgcn_global_load_lds((gbl_void*)(s_src + ((size_t)t * kSteps + kk) * 4),
                                        (lds_void*)(sbase + kk * kScaleStep), 4, 0, 0);
   };
 
-  // Fragment reads: lane l reads row (l&15) of a 16-row block at logical chunk l>>4 (4 + l>>4).
-  const int frow = lane & 15, fgrp = lane >> 4;
-  const int foff0 = frow * 128 + ((fgrp ^ (frow >> 1)) << 4);
-  const int a_off = wm * 128 * 128 + foff0;
-  const int b_off = kTileBytes + wn * 64 * 128 + foff0;
-  // Scale reads: byte l>>4 (the block whose scale this lane supplies) of the row's dword.
-  const int sa_off = (wm * 128 + frow) * 4 + fgrp;
-  const int sb_off = (TM + wn * 64 + frow) * 4 + fgrp;
+  // Scale reads: byte l>>4 (the block whose scale this lane supplies) of the dword of the lane's
+  // row, wm * 128 + frow of A's 256 dwords and wn * 64 + frow of Bt's behind them.
+  const int sa_off = c.wm * 512 + c.frow * 4 + (c.lane >> 4);
+  const int sb_off = TM * 4 + c.wn * 256 + c.frow * 4 + (c.lane >> 4);
 
   f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  tile_zero(acc);
 
   const int nt = K / gm_mx_tile_k(FMT);
   stage(0, 0);
@@ -141,12 +111,12 @@ __device__ __forceinline__ void mxgemm_nt_block(const uint8_t* __restrict__ A,
       int bsc[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        bfr[j] = mx_fragment<FMT>(sb, b_off + j * 2048, kk);
+        bfr[j] = mx_fragment<FMT>(sb, c.b_off + j * 2048, kk);
         bsc[j] = ss[kk * kScaleStep + sb_off + j * 64];
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const i32x8 af = mx_fragment<FMT>(sb, a_off + i * 2048, kk);
+        const i32x8 af = mx_fragment<FMT>(sb, c.a_off + i * 2048, kk);
         const int asc = ss[kk * kScaleStep + sa_off + i * 64];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -158,18 +128,7 @@ __device__ __forceinline__ void mxgemm_nt_block(const uint8_t* __restrict__ A,
     __syncthreads();
   }
 
-  // Epilogue: C/D map of the 16x16 shapes: col = l&15, row = 4(l>>4) + reg.
-  const int crow = tm * TM + wm * 128 + 4 * (lane >> 4);
-  const int ccol = tn * TN + wn * 64 + (lane & 15);
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        C[(size_t)(crow + i * 16 + r) * N + ccol + j * 16] =
-            kTraced && i == 0 && j == 0 && r == 0 ? bf16_flipped(acc[0][0][0], flip)
-                                                  : (__bf16)acc[i][j][r];
+  tile_store<kTraced>(c, C, N, tm, tn, acc, flip);
 }
 
 template <int FMT>
@@ -225,6 +184,48 @@ bool shape_ok(int fmt, int M, int N, int K) {
          N % mx256::TN == 0 && K % gm_mx_tile_k(fmt) == 0;
 }
 
+// What both GEMM entry points take: a shape of the format's, and pointers as the kernels'
+// 16-byte operand loads, 4-byte scale loads and 2-byte stores need them.
+bool gemm_args_ok(int fmt, const void* A, const void* sA, const void* Bt, const void* sB,
+                  const void* C, int M, int N, int K) {
+  return shape_ok(fmt, M, N, K) && A && sA && Bt && sB && C && !((uintptr_t)A & 15) &&
+         !((uintptr_t)Bt & 15) && !((uintptr_t)sA & 3) && !((uintptr_t)sB & 3) &&
+         !((uintptr_t)C & 1);
+}
+
+template <int FMT>
+const void* kernel_of(bool traced) {
+  return traced ? (const void*)k_mxgemm_nt_traced<FMT> : (const void*)k_mxgemm_nt<FMT>;
+}
+int mx_kernel_regs(int fmt, bool traced, int* num_regs, int* scratch_bytes) {
+  if (!gm_mx_format_ok(fmt)) return (int)hipErrorInvalidValue;
+  return kernel_regs(fmt == GM_MX_FP4 ? kernel_of<GM_MX_FP4>(traced) : kernel_of<GM_MX_FP8>(traced),
+                     num_regs, scratch_bytes);
+}
+
+// The MX burn-ins' operands (gm_gemm_shared.h, "the burn-in driver"): random-class fills.
+struct BurnInMx {
+  int fmt;
+  DevBuf da, db, dsa, dsb;
+  explicit BurnInMx(int fmt) : fmt(fmt) {}
+  static bool shape_ok(int fmt, int n) { return ::shape_ok(fmt, n, n, n); }
+  int fill(int n) {
+    const size_t eb = (size_t)n * gm_mx_row_bytes(fmt, (size_t)n), sb = (size_t)n * n / GM_MX_BLOCK;
+    GM_CHECK(da.alloc(eb));
+    GM_CHECK(db.alloc(eb));
+    GM_CHECK(dsa.alloc(sb));
+    GM_CHECK(dsb.alloc(sb));
+    const int e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0x5151u, n, n, da.p, dsa.p, nullptr);
+    return e ? e : gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0xa3a3u, n, n, db.p, dsb.p, nullptr);
+  }
+  int gemm(void* c, int n) const {
+    return gm_probe_mxgemm_nt(fmt, da.p, dsa.p, db.p, dsb.p, c, n, n, n, nullptr);
+  }
+  int gemm_traced(void* c, int n, const GemmTrace& tr) const {
+    return launch_mxgemm_traced(fmt, da.p, dsa.p, db.p, dsb.p, c, n, n, n, tr, nullptr);
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -244,9 +245,7 @@ int gm_probe_mx_fill(int fmt, int cls, uint32_t seed, int rows, int K, void* ele
 int gm_probe_mxgemm_nt(int fmt, const void* A, const void* sA, const void* Bt, const void* sB,
                        void* C, int M, int N, int K, void* stream) {
   using namespace mx256;
-  if (!shape_ok(fmt, M, N, K) || !A || !sA || !Bt || !sB || !C || ((uintptr_t)A & 15) ||
-      ((uintptr_t)Bt & 15) || ((uintptr_t)sA & 3) || ((uintptr_t)sB & 3) || ((uintptr_t)C & 1))
-    return (int)hipErrorInvalidValue;
+  if (!gemm_args_ok(fmt, A, sA, Bt, sB, C, M, N, K)) return (int)hipErrorInvalidValue;
   const dim3 grid((M / TM) * (N / TN)), block(kThreads);
   if (fmt == GM_MX_FP4)
     hipLaunchKernelGGL(k_mxgemm_nt<GM_MX_FP4>, grid, block, 0, (hipStream_t)stream,
@@ -269,39 +268,14 @@ int gm_probe_mxgemm_expected(int fmt, int cls, uint32_t seed_a, uint32_t seed_b,
 }
 
 int gm_probe_mxgemm_kernel_info(int fmt, int* num_regs, int* scratch_bytes) {
-  if (!gm_mx_format_ok(fmt) || !num_regs || !scratch_bytes) return (int)hipErrorInvalidValue;
-  hipFuncAttributes attr;
-  GM_CHECK(hipFuncGetAttributes(&attr, fmt == GM_MX_FP4 ? (const void*)k_mxgemm_nt<GM_MX_FP4>
-                                                        : (const void*)k_mxgemm_nt<GM_MX_FP8>));
-  *num_regs = attr.numRegs;
-  *scratch_bytes = (int)attr.localSizeBytes;
-  return 0;
+  return mx_kernel_regs(fmt, false, num_regs, scratch_bytes);
 }
 
 int gm_probe_mx_burn_in_flip(int dev, int fmt, int n, double seconds, int n_flips,
                              const uint64_t* flip_elems, const uint16_t* flip_masks,
                              double* tflops, uint64_t* mismatches, int* iters) {
-  *tflops = 0;
-  *mismatches = 0;
-  *iters = 0;
-  if (!shape_ok(fmt, n, n, n) || seconds <= 0) return (int)hipErrorInvalidValue;
-  if (!burn_in_flips_ok((size_t)n * n, n_flips, flip_elems, flip_masks))
-    return (int)hipErrorInvalidValue;
-  DeviceGuard g(dev);
-  if (!g.ok) return (int)hipErrorInvalidDevice;
-  const size_t eb = (size_t)n * gm_mx_row_bytes(fmt, (size_t)n), sb = (size_t)n * n / GM_MX_BLOCK;
-  DevBuf da, db, dsa, dsb;
-  GM_CHECK(da.alloc(eb));
-  GM_CHECK(db.alloc(eb));
-  GM_CHECK(dsa.alloc(sb));
-  GM_CHECK(dsb.alloc(sb));
-  int e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0x5151u, n, n, da.p, dsa.p, nullptr);
-  if (!e) e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0xa3a3u, n, n, db.p, dsb.p, nullptr);
-  if (e) return e;
-  return burn_in_loop(
-      n, seconds, n_flips, flip_elems, flip_masks,
-      [&](void* c) { return gm_probe_mxgemm_nt(fmt, da.p, dsa.p, db.p, dsb.p, c, n, n, n, nullptr); },
-      tflops, mismatches, iters);
+  return burn_in_run<BurnInMx>(fmt, dev, n, seconds, n_flips, flip_elems, flip_masks, tflops,
+                               mismatches, iters);
 }
 
 // ------------------------------------------------------------------ attributed burn-in
@@ -311,9 +285,7 @@ int gm_probe_mxgemm_nt_traced(int fmt, const void* A, const void* sA, const void
                               uint32_t* cu_of_tile, const gm_burnin_inject_t* inject,
                               void* stream) {
   using namespace mx256;
-  if (!shape_ok(fmt, M, N, K) || !A || !sA || !Bt || !sB || !C || ((uintptr_t)A & 15) ||
-      ((uintptr_t)Bt & 15) || ((uintptr_t)sA & 3) || ((uintptr_t)sB & 3) || ((uintptr_t)C & 1))
-    return (int)hipErrorInvalidValue;
+  if (!gemm_args_ok(fmt, A, sA, Bt, sB, C, M, N, K)) return (int)hipErrorInvalidValue;
   if (r < 0 || r >= (M / TM) * (N / TN) || !cu_of_tile || ((uintptr_t)cu_of_tile & 3) ||
       !burn_in_inject_ok(inject) || (inject && inject->first))
     return (int)hipErrorInvalidValue;
@@ -324,14 +296,7 @@ int gm_probe_mxgemm_nt_traced(int fmt, const void* A, const void* sA, const void
 }
 
 int gm_probe_mxgemm_nt_traced_info(int fmt, int* num_regs, int* scratch_bytes) {
-  if (!gm_mx_format_ok(fmt) || !num_regs || !scratch_bytes) return (int)hipErrorInvalidValue;
-  hipFuncAttributes attr;
-  GM_CHECK(hipFuncGetAttributes(&attr, fmt == GM_MX_FP4
-                                           ? (const void*)k_mxgemm_nt_traced<GM_MX_FP4>
-                                           : (const void*)k_mxgemm_nt_traced<GM_MX_FP8>));
-  *num_regs = attr.numRegs;
-  *scratch_bytes = (int)attr.localSizeBytes;
-  return 0;
+  return mx_kernel_regs(fmt, true, num_regs, scratch_bytes);
 }
 
 int gm_probe_mx_burn_in_attr(int dev, int fmt, int n, double seconds, int n_flips,
@@ -339,32 +304,9 @@ int gm_probe_mx_burn_in_attr(int dev, int fmt, int n, double seconds, int n_flip
                              const gm_burnin_inject_t* inject, double* tflops,
                              uint64_t* mismatches, int* iters, gm_burnin_attr_t* attr,
                              gm_burnin_blamed_t* blamed, int blamed_cap) {
-  *tflops = 0;
-  *mismatches = 0;
-  *iters = 0;
-  if (!attr || blamed_cap < 0 || (blamed_cap > 0 && !blamed)) return (int)hipErrorInvalidValue;
-  *attr = gm_burnin_attr_t{};
-  if (!shape_ok(fmt, n, n, n) || seconds <= 0 || !burn_in_inject_ok(inject))
-    return (int)hipErrorInvalidValue;
-  if (!burn_in_flips_ok((size_t)n * n, n_flips, flip_elems, flip_masks))
-    return (int)hipErrorInvalidValue;
-  DeviceGuard g(dev);
-  if (!g.ok) return (int)hipErrorInvalidDevice;
-  const size_t eb = (size_t)n * gm_mx_row_bytes(fmt, (size_t)n), sb = (size_t)n * n / GM_MX_BLOCK;
-  DevBuf da, db, dsa, dsb;
-  GM_CHECK(da.alloc(eb));
-  GM_CHECK(db.alloc(eb));
-  GM_CHECK(dsa.alloc(sb));
-  GM_CHECK(dsb.alloc(sb));
-  int e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0x5151u, n, n, da.p, dsa.p, nullptr);
-  if (!e) e = gm_probe_mx_fill(fmt, GM_MX_RANDOM, 0xa3a3u, n, n, db.p, dsb.p, nullptr);
-  if (e) return e;
-  return burn_in_attr_loop(
-      n, seconds, n_flips, flip_elems, flip_masks, inject,
-      [&](void* c, const GemmTrace& tr) {
-        return launch_mxgemm_traced(fmt, da.p, dsa.p, db.p, dsb.p, c, n, n, n, tr, nullptr);
-      },
-      tflops, mismatches, iters, attr, blamed, blamed_cap);
+  const BurnInAttr at{inject, attr, blamed, blamed_cap};
+  return burn_in_run<BurnInMx>(fmt, dev, n, seconds, n_flips, flip_elems, flip_masks, tflops,
+                               mismatches, iters, &at);
 }
 
 }  // extern "C"

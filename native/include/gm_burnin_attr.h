@@ -37,7 +37,7 @@ GM_BURNIN_HD void gm_gemm_tile_map(int block, int grid, int M, int N, int r, int
   tn = (wgid % per_group) / gsize;
 }
 
-// The geometry of the two burn-in GEMMs (g256 in gm_gemm.hip, mx256 in gm_mxgemm.hip).
+// The geometry of the two burn-in GEMMs (tile256 in hip/gm_gemm_shared.h).
 constexpr int kBurninTile = 256, kBurninGroupM = 8;
 
 inline int gm_burnin_gcd(int a, int b) {

@@ -629,6 +629,8 @@ def test_read_refuses_bad_arguments():
 
 # ------------------------------------------------------------------ gemm_nt on exact data
 GEMM_SHAPES = [(256, 256, 128),      # two K-tiles: V5's stage(1, TK) fires, stage(cur, ..) never
+               (256, 256, 192),      # three, an odd depth above 1: V5's stage(cur, (t+2)*TK)
+                                     # fires exactly once and the loop ends on buffer 0
                (256, 512, 256),      # four K-tiles, an even depth above 2
                (2560, 512, 64),      # ten tile rows: a full group of 8, then a partial one of 2;
                                      # 20 blocks, not a multiple of the 8 XCDs
