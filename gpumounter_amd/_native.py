@@ -383,6 +383,46 @@ class AtomicsResult(C.Structure):
                 ("seconds", C.c_double)]
 
 
+HOSTSYNC_MAX_RECORDS = 16     # native/include/gm_probe.h GM_HOSTSYNC_MAX_RECORDS
+HOSTSYNC_WHERE_STALE = 1      # GM_HOSTSYNC_WHERE_STALE
+HOSTSYNC_WHERE_LOST = 2       # GM_HOSTSYNC_WHERE_LOST
+
+
+class HostsyncRecord(C.Structure):
+    _fields_ = [("index", C.c_uint64), ("expected", C.c_uint64), ("got", C.c_uint64),
+                ("test", C.c_uint32), ("kind", C.c_uint32), ("where", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class HostsyncInject(C.Structure):
+    _fields_ = [("test", C.c_uint32), ("kind", C.c_uint32), ("a", C.c_uint32),
+                ("b", C.c_uint32), ("word", C.c_uint32), ("mask", C.c_uint32)]
+
+
+class HostsyncDir(C.Structure):
+    _fields_ = [("handoffs", C.c_uint64), ("observed", C.c_uint64), ("unseen", C.c_uint64),
+                ("stale_words", C.c_uint64), ("poll_max_us", C.c_double)]
+
+
+class HostsyncResult(C.Structure):
+    _fields_ = [("tests_run", C.c_uint32), ("tests_skipped", C.c_uint32),
+                ("atomics_supported", C.c_uint32), ("blocks", C.c_uint32),
+                ("host_threads", C.c_uint32), ("iters", C.c_uint32), ("spread", C.c_uint32),
+                ("rounds", C.c_uint32), ("lines", C.c_uint32), ("budget_us", C.c_uint32),
+                ("host_budget_us", C.c_uint32), ("cas_width", C.c_uint32),
+                ("words_in_error", C.c_uint64), ("add_u32_errors", C.c_uint64),
+                ("add_u64_errors", C.c_uint64), ("cas_errors", C.c_uint64),
+                ("tickets", C.c_uint64), ("holes", C.c_uint64), ("duplicates", C.c_uint64),
+                ("counter_errors", C.c_uint64), ("out_of_range", C.c_uint64),
+                ("swaps", C.c_uint64), ("swap_missing", C.c_uint64),
+                ("swap_duplicates", C.c_uint64), ("swap_foreign", C.c_uint64),
+                ("cas_giveups", C.c_uint64), ("host_ops_in_flight", C.c_uint64),
+                ("lost_words", C.c_uint64), ("dir", HostsyncDir * 2),
+                ("rtt_median_us", C.c_double), ("rtt_max_us", C.c_double),
+                ("ms", C.c_double * 5), ("records_filled", C.c_uint32), ("pad", C.c_uint32),
+                ("records", HostsyncRecord * HOSTSYNC_MAX_RECORDS), ("seconds", C.c_double)]
+
+
 def _prefer_torch_hip_runtime() -> None:
     """A process can hold only one HIP runtime, and ``libamdhip64.so.7`` is resolved by soname:
     whichever copy is loaded first (ROCm's /opt/rocm/lib or the one PyTorch bundles) serves
@@ -575,6 +615,25 @@ def probe() -> C.CDLL:
         lib.gm_probe_atomics.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                          C.POINTER(AtomicsInject), C.POINTER(AtomicsResult)]
+        u32, inj_p, res_p = C.c_uint32, C.POINTER(HostsyncInject), C.POINTER(HostsyncResult)
+        lib.gm_probe_hostsync_expected.argtypes = [u32, u32, u32, u32, u32, C.c_uint64,
+                                                   C.c_void_p, C.c_uint64]
+        lib.gm_probe_hostsync_cas_width.argtypes = [u32, u32, u32, u32, C.POINTER(u32)]
+        lib.gm_probe_hostsync_payload.argtypes = [C.c_uint64, u32, u32, u32, u32]
+        lib.gm_probe_hostsync_payload.restype = u32
+        lib.gm_probe_hostsync_supported.argtypes = [C.c_int, C.POINTER(C.c_int)]
+        lib.gm_probe_hostsync_add.argtypes = [u32, u32, u32, u32, u32, C.c_uint64, inj_p,
+                                              C.c_void_p, C.c_void_p, res_p]
+        lib.gm_probe_hostsync_ticket.argtypes = [u32, u32, u32, u32, C.c_uint64, inj_p,
+                                                 C.c_void_p, res_p]
+        lib.gm_probe_hostsync_swap.argtypes = [u32, u32, u32, u32, C.c_uint64, inj_p,
+                                               C.c_void_p, res_p]
+        lib.gm_probe_hostsync_cas.argtypes = [u32, u32, u32, u32, C.c_uint64, inj_p,
+                                              C.c_void_p, C.c_void_p, res_p]
+        lib.gm_probe_hostsync_handoff.argtypes = [u32, u32, u32, u32, u32, u32, C.c_uint64,
+                                                  inj_p, C.c_void_p, res_p]
+        lib.gm_probe_hostsync.argtypes = [C.c_int, u32, u32, u32, u32, u32, u32, u32, u32, u32,
+                                          C.c_uint64, inj_p, res_p]
         lib.gm_probe_strerror.argtypes = [C.c_int]
         lib.gm_probe_strerror.restype = C.c_char_p
         lib._gm_typed = True

@@ -23,6 +23,12 @@
                                        [--atomics-rounds N]                  # cross-XCC atomics
                                        [--atomics-inject add:KIND:G:S:MASK|cas:G:S:MASK|
                                                          ticket:G:S|handoff:BLOCK:ROUND:WORD:MASK]
+                                       [--host-sync] [--host-sync-tests add,ticket,swap,cas,handoff]
+                                       [--host-sync-blocks N] [--host-sync-threads N]
+                                       [--host-sync-rounds N]     # host-GPU atomics and hand-offs
+                                       [--host-sync-inject add:KIND:G:S:MASK|cas:G:S:MASK|
+                                                  ticket:G:S|swap:G:S:MASK|
+                                                  handoff:DIR:BLOCK:ROUND:WORD:MASK]
                                        [--mfma-scan] [--mfma-scan-formats f16,fp8,...,mxfp4]
                                        [--mfma-scan-iters N] [--mfma-scan-rounds N]
                                        [--mfma-scan-inject ID|any:FORMAT:THREAD:WORD:MASK]
@@ -43,6 +49,7 @@
     python -m gpumounter_amd doctor  [--json] [--skip-cluster] [--gpu [--burn-in 30]]  # preflight
                                      [--gpu --memtest [SIZE]] [--gpu --cu-scan]
                                      [--gpu --host-link [SIZE]] [--gpu --atomics]
+                                     [--gpu --host-sync]
                                      [--gpu --mfma-scan] [--gpu --lane-scan]
                                      [--gpu --cache-scan]
     python -m gpumounter_amd config-doc > docs/CONFIG.md   # every GM_* setting, from the source
@@ -227,6 +234,28 @@ def _add_atomics(p, what: str) -> None:
                    metavar="TEST:...",
                    help="negative control: add:KIND:G:S:MASK, cas:G:S:MASK, ticket:G:S or "
                         "handoff:BLOCK:ROUND:WORD:MASK; the test must report it")
+
+
+def _hostsync_arg(kind):
+    """argparse type for the --host-sync-* options: the parser in ops.hostsync, its refusal a
+    usage error."""
+    def conv(text):
+        from gpumounter_amd.ops import hostsync
+        try:
+            return getattr(hostsync, kind)(text)
+        except hostsync.ProbeError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    conv.__name__ = kind
+    return conv
+
+
+def _add_hostsync(p, what: str) -> None:
+    p.add_argument("--host-sync", action="store_true", help=what)
+    p.add_argument("--host-sync-inject", type=_hostsync_arg("parse_inject"), default=None,
+                   metavar="TEST:...",
+                   help="negative control: add:KIND:G:S:MASK, cas:G:S:MASK, ticket:G:S, "
+                        "swap:G:S:MASK or handoff:DIR:BLOCK:ROUND:WORD:MASK; the test must "
+                        "report it")
 
 
 def _scans():
@@ -416,6 +445,35 @@ def cmd_probe(args) -> int:
             print(f"probe: --atomics-inject into {inj[0]!r}, which --atomics-tests leaves out",
                   file=sys.stderr)
             return 2
+    if not args.host_sync:
+        given = [o for o, v in (("--host-sync-inject", args.host_sync_inject),
+                                ("--host-sync-tests", args.host_sync_tests),
+                                ("--host-sync-blocks", args.host_sync_blocks),
+                                ("--host-sync-threads", args.host_sync_threads),
+                                ("--host-sync-rounds", args.host_sync_rounds)) if v is not None]
+        if given:
+            print(f"probe: {given[0]} needs --host-sync", file=sys.stderr)
+            return 2
+    else:
+        from gpumounter_amd.ops import hostsync as _hs
+
+        for value, name, lo, hi in (
+                (args.host_sync_blocks, "--host-sync-blocks", 1, _hs.MAX_BLOCKS),
+                (args.host_sync_threads, "--host-sync-threads", 0, _hs.MAX_HOST_THREADS),
+                (args.host_sync_rounds, "--host-sync-rounds", 1, _hs.MAX_ROUNDS)):
+            if value is not None and not lo <= value <= hi:
+                print(f"probe: {name} must be between {lo} and {hi}", file=sys.stderr)
+                return 2
+        tests = args.host_sync_tests or _hs.ALL_TESTS
+        inj = args.host_sync_inject
+        if inj and inj[0] not in tests:
+            print(f"probe: --host-sync-inject into {inj[0]!r}, which --host-sync-tests leaves "
+                  f"out", file=sys.stderr)
+            return 2
+        if args.host_sync_threads == 0 and "handoff" in tests:
+            print("probe: the hand-off needs --host-sync-threads of at least 1 (or leave it out "
+                  "with --host-sync-tests)", file=sys.stderr)
+            return 2
     for scan in later:
         error = _scan_usage(scan, args, "probe")
         if error:
@@ -467,6 +525,18 @@ def cmd_probe(args) -> int:
                 rounds=args.atomics_rounds or atomics.DEFAULT_ROUNDS,
                 _inject=args.atomics_inject)
             bad |= not r["atomics"]["ok"]
+    if args.host_sync:
+        from gpumounter_amd.ops import hostsync
+
+        for r in res:
+            r["hostsync"] = hostsync.run(
+                r["device"], tests=args.host_sync_tests or hostsync.ALL_TESTS,
+                blocks=args.host_sync_blocks or 0,
+                host_threads=(hostsync.DEFAULT_HOST_THREADS if args.host_sync_threads is None
+                              else args.host_sync_threads),
+                rounds=args.host_sync_rounds or hostsync.DEFAULT_ROUNDS,
+                _inject=args.host_sync_inject)
+            bad |= not r["hostsync"]["ok"]
     for scan in later:
         bad |= not _run_scan(scan, args, res)
     print(json.dumps(res, indent=2))
@@ -629,6 +699,9 @@ def cmd_doctor(args) -> int:
     if args.atomics_inject and not args.atomics:
         print("doctor: --atomics-inject needs --atomics", file=sys.stderr)
         return 2
+    if args.host_sync_inject and not args.host_sync:
+        print("doctor: --host-sync-inject needs --host-sync", file=sys.stderr)
+        return 2
     if _burn_in_usage(args, "doctor"):
         return 2
     for value, name in ((args.burn_in_format, "burn_in_formats"),
@@ -641,6 +714,10 @@ def cmd_doctor(args) -> int:
         extra["atomics"] = True
         if args.atomics_inject:
             extra["atomics_inject"] = args.atomics_inject
+    if args.host_sync:
+        extra["host_sync"] = True
+        if args.host_sync_inject:
+            extra["host_sync_inject"] = args.host_sync_inject
     scans = _scans()
     for scan in scans:
         error = _scan_usage(scan, args, "doctor")
@@ -654,7 +731,7 @@ def cmd_doctor(args) -> int:
                     extra[f"{scan.stem}_{name}"] = getattr(args, f"{scan.stem}_{name}")
     checks = doctor.run(cfg, skip_cluster=args.skip_cluster,
                         gpu=(args.gpu or bool(args.burn_in) or bool(memtest_bytes)
-                             or args.host_link is not None or args.atomics
+                             or args.host_link is not None or args.atomics or args.host_sync
                              or any(getattr(args, scan.stem) for scan in scans)),
                         burn_in_s=args.burn_in, memtest_bytes=memtest_bytes, **extra)
     print(doctor.render(checks, args.json))
@@ -728,6 +805,18 @@ def build_parser() -> argparse.ArgumentParser:
                    help="blocks of 256 threads, 1..4096 (default: one per CU)")
     p.add_argument("--atomics-rounds", type=int, default=None, metavar="N",
                    help="hand-off rounds, 1..64 (default 8)")
+    _add_hostsync(p, "host-GPU atomics and hand-off test of every probed GPU: system-scope "
+                     "atomics on pinned host memory with host threads contending, and "
+                     "release/acquire hand-offs through flags in host memory in both directions "
+                     "(exit 1 on any wrong, lost or stale word)")
+    p.add_argument("--host-sync-tests", type=_hostsync_arg("parse_tests"), default=None,
+                   metavar="a,b,...", help="of add,ticket,swap,cas,handoff (default: all)")
+    p.add_argument("--host-sync-blocks", type=int, default=None, metavar="N",
+                   help="blocks of 256 threads, 1..CUs (default: min(16, CUs))")
+    p.add_argument("--host-sync-threads", type=int, default=None, metavar="N",
+                   help="host threads, 0..8 (default 2; the hand-off needs one)")
+    p.add_argument("--host-sync-rounds", type=int, default=None, metavar="N",
+                   help="hand-off rounds, 1..64 (default 8)")
     for scan in later:
         _add_probe_scan(p, scan)
     p.set_defaults(fn=cmd_probe)
@@ -770,6 +859,7 @@ def build_parser() -> argparse.ArgumentParser:
     _add_hostlink_size(p, "with --gpu: host link (PCIe) test of every GPU over SIZE bytes of "
                           "pinned host memory per buffer (default 256M)")
     _add_atomics(p, "with --gpu: cross-XCC atomics and coherence test of every GPU")
+    _add_hostsync(p, "with --gpu: host-GPU atomics and hand-off test of every GPU")
     for scan in later:
         _add_doctor_scan(p, scan)
     p.set_defaults(fn=cmd_doctor)

@@ -16,8 +16,8 @@ No kernel waits without a bound on another block, so a call ends on any device s
 whose flag was not seen within the budget is counted (``unseen``) and is not an error. XCC ids are
 labels read from the hardware registers; no result depends on where a block ran.
 
-What it cannot tell: system-scope or fine-grained memory, LDS atomics, several GPUs, a hand-off
-under a tenant's load. The counter a ticket is drawn from is computed at run time, so the compiler
+What it cannot tell: system-scope or host memory (``ops.hostsync`` has those), LDS atomics,
+several GPUs, a hand-off under a tenant's load. The counter a ticket is drawn from is computed at run time, so the compiler
 does not fold a wave's draws into one add: per-lane returning atomics reach the hardware at every
 ``spread`` (checked in the assembly, profiles/atomics/README.md).
 No silent fallback: a missing ``libgm_probe.so`` or a HIP failure raises.

@@ -24,18 +24,22 @@ starting a job on them — the reference offers nothing here:
 8. optionally (``--atomics``) the cross-XCC atomics and coherence test on all GPUs at once
    (:func:`gpumounter_amd.ops.atomics.run`): known-answer atomics of ten kinds, tickets, a CAS
    loop and in-launch hand-offs between blocks with the agent-scope release and acquire;
-9. optionally (``--mfma-scan``) the per-CU matrix-core format scan on all GPUs at once
+9. optionally (``--host-sync``) the host-GPU atomics and hand-off test on all GPUs at once
+   (:func:`gpumounter_amd.ops.hostsync.run`): system-scope atomics on pinned host memory with two
+   host threads per GPU contending, and release/acquire hand-offs through flags in host memory
+   in both directions;
+10. optionally (``--mfma-scan``) the per-CU matrix-core format scan on all GPUs at once
    (:func:`gpumounter_amd.ops.mfmascan.scan`): bit-exact MFMAs in f16, fp8, bf8, i8, f32, f64 and
    the block-scaled fp8, bf8, fp6, bf6 and fp4 forms on every compute unit;
-10. optionally (``--lane-scan``) the per-CU register, lane and scalar-unit scan on all GPUs at once
+11. optionally (``--lane-scan``) the per-CU register, lane and scalar-unit scan on all GPUs at once
    (:func:`gpumounter_amd.ops.lanescan.scan`): bit-exact cross-lane moves, a register-file march,
    a scalar chain, transcendentals at exact points, fp64 and packed arithmetic on every compute
    unit;
-11. optionally (``--cache-scan``) the per-CU cache scan on all GPUs at once
+12. optionally (``--cache-scan``) the per-CU cache scan on all GPUs at once
    (:func:`gpumounter_amd.ops.cachescan.scan`): a march served by the L2, hit and replacement
    passes through the vector L1, a pointer chase through the scalar data cache and a body larger
    than the instruction cache on every compute unit;
-12. optionally (``--lds-scan``) the per-CU LDS scan on all GPUs at once
+13. optionally (``--lds-scan``) the per-CU LDS scan on all GPUs at once
    (:func:`gpumounter_amd.ops.ldsscan.scan`): sub-dword, wide and paired LDS accesses, the LDS
    atomics, the bank crossbar at every conflict degree, the transposing read and direct
    global-to-LDS loads on every compute unit.
@@ -130,6 +134,10 @@ def main(argv=None) -> int:
                     help="then the cross-XCC atomics and coherence test on every GPU at once")
     ap.add_argument("--atomics-inject", default=None, metavar="TEST:...",
                     help="its negative control (see probe --atomics-inject); needs --atomics")
+    ap.add_argument("--host-sync", action="store_true",
+                    help="then the host-GPU atomics and hand-off test on every GPU at once")
+    ap.add_argument("--host-sync-inject", default=None, metavar="TEST:...",
+                    help="its negative control (see probe --host-sync-inject); needs --host-sync")
     for scan in later:
         ap.add_argument(f"--{scan.label}", action="store_true",
                         help=f"then the {scan.title}{scan.covers} on every GPU at once")
@@ -164,6 +172,15 @@ def main(argv=None) -> int:
         try:
             atomics_inject = atomics.parse_inject(args.atomics_inject)
         except atomics.ProbeError as e:
+            ap.error(str(e))
+    host_sync_inject = None
+    if args.host_sync_inject is not None:
+        from gpumounter_amd.ops import hostsync
+        if not args.host_sync:
+            ap.error("--host-sync-inject needs --host-sync")
+        try:
+            host_sync_inject = hostsync.parse_inject(args.host_sync_inject)
+        except hostsync.ProbeError as e:
             ap.error(str(e))
     hostlink_bytes = None
     if args.host_link not in (None, "auto"):
@@ -252,6 +269,17 @@ def main(argv=None) -> int:
             #                               "first_errors" names the XCCs then
         report["atomics"] = at
         report["ok"] &= all(a["ok"] for a in at)
+    if args.host_sync and not args.cpu_ranks:
+        from concurrent.futures import ThreadPoolExecutor
+
+        from gpumounter_amd.ops import hostsync
+
+        # all GPUs at once: they share the host's memory and its root complex; two host threads
+        # per GPU
+        with ThreadPoolExecutor(max_workers=world) as ex:
+            hs = list(ex.map(lambda d: hostsync.run(d, _inject=host_sync_inject), range(world)))
+        report["hostsync"] = hs
+        report["ok"] &= all(h["ok"] for h in hs)
     for scan in later if not args.cpu_ranks else ():
         _run_scan(scan, args, controls, world, report)
     print(json.dumps(report))

@@ -306,7 +306,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                cache_scan_inject=None, cache_scan_poke=None,
                burn_in_formats=("bf16",), lds_scan: bool = False,
                lds_scan_inject=None, lds_scan_poke=None, burn_in_attribute: bool = False,
-               burn_in_inject=None) -> List[Check]:
+               burn_in_inject=None, host_sync: bool = False,
+               host_sync_inject=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
     sustained bit-checked GEMM load per GPU, once per format in ``burn_in_formats`` (bf16, and the
@@ -340,8 +341,14 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     ``cache_scan_inject`` and ``cache_scan_poke`` are its negative controls. With ``lds_scan``
     also the per-CU LDS scan (:func:`gpumounter_amd.ops.ldsscan.scan`: access widths, LDS atomics,
     bank crossbar, transposing read, global-to-LDS loads), failed, named and stated in the same
-    way; ``lds_scan_inject`` and ``lds_scan_poke`` are its negative controls. A GPU that fails
-    here should not be handed out."""
+    way; ``lds_scan_inject`` and ``lds_scan_poke`` are its negative controls. With ``host_sync``
+    also the host-GPU atomics and hand-off test (:func:`gpumounter_amd.ops.hostsync.run`), after
+    the atomics test: a wrong table word, a lost or doubled ticket, a missing, doubled or foreign
+    swap value, a given-up CAS or a stale or lost hand-off word fails the check and names the
+    test, the direction and the first record; hand-offs not seen within the budgets do not, but
+    the check warns when a direction saw none at all, and when the device reports no native host
+    atomics so that the atomic tests were skipped; ``host_sync_inject`` is its negative control.
+    A GPU that fails here should not be handed out."""
     given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import cuframe, mxgemm, probe
@@ -432,6 +439,27 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                 elif a["handoff_vacuous"]:
                     detail += ", no hand-off was seen within the budget: it proved nothing"
                     status = "warn" if status == "ok" else status
+            if host_sync:
+                from gpumounter_amd.ops import hostsync as hs
+
+                h = hs.run(d, _inject=host_sync_inject)
+                detail += (f", host-sync {'+'.join(h['tests'])} {h['blocks']} blocks and "
+                           f"{h['host_threads']} host threads {h['seconds'] * 1e3:.0f} ms "
+                           f"{h['words_in_error']} wrong words, hand-offs "
+                           f"{h['h2d']['observed']}/{h['h2d']['handoffs']} seen by the GPU "
+                           f"{h['d2h']['observed']}/{h['d2h']['handoffs']} by the host")
+                if not h["ok"]:
+                    detail += f", failed: {hs.describe_failed(h)}"
+                    status = "fail"
+                else:
+                    if h["handoff_vacuous"]:
+                        detail += (", a direction saw no hand-off within its budget: it proved "
+                                   "nothing there")
+                        status = "warn" if status == "ok" else status
+                    if h["tests_skipped"]:
+                        detail += (f", skipped {'+'.join(h['tests_skipped'])}: "
+                                   f"{hs.NO_ATOMICS}")
+                        status = "warn" if status == "ok" else status
             for scan in later:
                 text, failed = _scan_segment(scan, d, given)
                 detail, status = detail + text, "fail" if failed else status
@@ -451,7 +479,8 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         lane_scan_inject=None, cache_scan: bool = False, cache_scan_inject=None,
         cache_scan_poke=None, burn_in_formats=None, burn_in_flip=None,
         lds_scan: bool = False, lds_scan_inject=None, lds_scan_poke=None,
-        burn_in_attribute: bool = False, burn_in_inject=None) -> List[Check]:
+        burn_in_attribute: bool = False, burn_in_inject=None, host_sync: bool = False,
+        host_sync_inject=None) -> List[Check]:
     given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.ops import cuframe
 
@@ -473,6 +502,10 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
             extra["atomics"] = True
             if atomics_inject is not None:
                 extra["atomics_inject"] = atomics_inject
+        if host_sync:
+            extra["host_sync"] = True
+            if host_sync_inject is not None:
+                extra["host_sync_inject"] = host_sync_inject
         for scan in cuframe.scans():
             if given[scan.stem]:
                 extra[scan.stem] = True

@@ -1309,8 +1309,191 @@ int gm_probe_atomics(int dev, uint32_t tests_mask, uint32_t blocks, uint32_t ite
                      uint32_t spread, uint32_t rounds, uint32_t lines, uint32_t budget_us,
                      uint64_t seed, const gm_atomics_inject_t* inject, gm_atomics_result_t* out);
 
+// ------------------------------------------------------- host-GPU atomics and hand-off test
+// Checks how a tenant's host code and its kernels synchronise: system-scope atomics on pinned
+// host memory, which travel as PCIe AtomicOps, and release/acquire hand-offs through flags in
+// host memory, in both directions, while a kernel runs (gm_hostsync.hip; value functions and
+// audits: gm_hostsync_ref.h, which defines the GM_HOSTSYNC_* test bits and limits; the host
+// threads' side, plain C++: gm_hostsync_host.h). It is per link, not per CU.
+//
+// Memory: every shared word (tables, counters, marks, flags, mailboxes) lies in
+// hipHostMalloc(Mapped | Coherent) memory, zeroed by the host before the launch, and the kernels
+// reach it through hipHostGetDevicePointer. The GPU side uses __hip_atomic_* at
+// __HIP_MEMORY_SCOPE_SYSTEM, the host side the __atomic_* builtins on the same words, relaxed
+// unless stated. Only what PCIe carries natively is exercised: fetch-add (32 and 64 bit, with
+// and without return), swap and compare-and-swap. hipDeviceAttributeHostNativeAtomicSupported is
+// reported as atomics_supported; where it is 0 the four atomic tests are not launched and are
+// listed in tests_skipped.
+//
+// Participants: `blocks` GPU blocks of 256 threads (1 .. CU count; 0 in the driver:
+// min(16, CUs)) and `host_threads` std::threads (0..8) inside the entry point, joined on every
+// return path, which make no HIP call. In the atomic tests host thread j plays block blocks + j:
+// it walks t < 256, s < iters with the same value functions, concurrently with the kernel. So
+// with B = blocks + host_threads the expected tables are those of the atomics test over B blocks
+// (H, a(g, s), op64, the draw, the CAS width rule: gm_atomics_ref.h), g = 256 block + t.
+// B * 256 * iters <= 2^20, iters <= 1024. A host thread starts when it reads the `ready` word the
+// kernel stores (system scope) at its start, or after 2 s. host_ops_in_flight counts the host
+// operations made while the kernel's end event was still hipErrorNotReady; it is informational.
+//
+// GM_HOSTSYNC_ADD 1: no-return fetch-add, u32 and u64 (atomics kinds 0 and 1), each into a table
+// of `spread` words; the final table equals the host fold, compared on the host after the join.
+// GM_HOSTSYNC_TICKET 2: as GM_ATOMICS_TICKET with K = spread counters and the marks in host
+// memory, GPU and host drawing from the same counters; the host audits holes, duplicates and
+// counter_errors; out_of_range is counted by whoever drew the ticket.
+// GM_HOSTSYNC_SWAP 4: operation (g, s) does old = exchange(word[a(g, s)], token),
+// token = 1 + 1024 g + s (u32), W = spread, and records old (a device buffer for GPU threads, a
+// host vector for played ones). Per word w the returned values of the operations into w plus the
+// final word[w] must be the tokens of those operations plus one 0, each once: swap_missing (a
+// token or the 0 is absent), swap_duplicates (a value seen n > 1 times: n - 1), swap_foreign (a
+// value that is no token of that word).
+// GM_HOSTSYNC_CAS 8: as GM_ATOMICS_CAS over B blocks, the table widened by the same rule; a
+// participant gives an operation up after as many failed exchanges as the host counted
+// operations into that word (every failure implies another's success, whoever contends).
+// GM_HOSTSYNC_HANDOFF 16: a ping-pong per block; host thread b mod host_threads serves block b
+// (host_threads >= 1). Every round has its own flag words, each on a 128-byte line of its own,
+// none reused; a payload is `lines` x 4 KiB (1 or 16),
+//   E(dir, b, r, word) = H_cuscan(0x600 + dir, b << 20 | r << 14 | word)    dir 0: host to device
+// For r < rounds: (1) the host plain-stores E(0, b, r, .) and store-releases flagH[b][r] = r + 1;
+// (2) the block: every thread plain-loads its payload bytes; lane 0 polls flagH[b][r] with
+// relaxed system loads until it reads r + 1 or wall_clock64() has advanced budget_us; seen: lane
+// 0's system acquire fence, s_waitcnt vmcnt(0), barrier, every thread plain-loads and compares
+// every word (stale_words of direction 0); not seen: unseen += 1, the block goes on; (3) the
+// block plain-stores E(1, b, r, .) to its host mailbox, 16 bytes per thread per line; every wave
+// s_waitcnt vmcnt(0); barrier; lane 0: system release fence, s_waitcnt vmcnt(0), relaxed system
+// store of flagD[b][r] = seen << 16 | r + 1; (4) the host polls flagD[b][r] with acquire loads
+// until its low half reads r + 1 or host_budget_us of steady_clock have passed; seen: it compares
+// every word (stale_words of direction 1); not seen: unseen += 1 and on to r + 1. After the join
+// and the stream's end the host audits every payload word and flag of both directions again
+// (lost_words). An unseen hand-off is legal. poll_max_us is the longest poll that ended in a
+// flag seen (taken before the last load); rtt_* the host-measured time from the flag store of
+// (1) to the flag seen in (4). Worst case for the kernel: rounds * budget_us, rounds <= 64,
+// budget_us <= 20000.
+//
+// Negative controls (gm_hostsync_inject_t; NULL: none). For ADD, TICKET, SWAP and CAS a = g may
+// name a host-played thread (g >= 256 blocks), which exercises the host path.
+//   ADD, CAS   (kind, a = g, b = s, mask): H of that one operation is XORed with mask
+//   TICKET     (a = g, b = s): that draw marks its first slot twice
+//   SWAP       (a = g, b = s, mask): that operation stores its token XOR mask
+//   HANDOFF    (kind = direction, a = block, b = round, word, mask): the producer stores that
+//              payload word XORed with mask
+//
+// Struct layout (checked by tests/test_hostsync.py): sizeof(gm_hostsync_record_t) = 40,
+// sizeof(gm_hostsync_inject_t) = 24, sizeof(gm_hostsync_dir_t) = 40,
+// sizeof(gm_hostsync_result_t) = 968 with words_in_error at byte 48, tickets at 80, swaps at 120,
+// cas_giveups at 152, host_ops_in_flight at 160, lost_words at 168, dir at 176, rtt_median_us at
+// 256, ms at 272, records_filled at 312, records at 320 and seconds at 960.
+#define GM_HOSTSYNC_MAX_RECORDS 16
+#define GM_HOSTSYNC_WHERE_STALE 1u   /* HANDOFF: found by the consumer while the kernel ran */
+#define GM_HOSTSYNC_WHERE_LOST 2u    /* HANDOFF: found by the audit after the launch */
+
+typedef struct gm_hostsync_record {
+  uint64_t index;           // table word; flat mark index, then the counters; SWAP: the word;
+                            // HANDOFF: block << 20 | round << 14 | word, a flag:
+                            // 1 << 40 | block << 6 | round
+  uint64_t expected;
+  uint64_t got;             // SWAP: the value that is foreign, missing or doubled there
+  uint32_t test;            // GM_HOSTSYNC_* bit
+  uint32_t kind;            // ADD: 0 u32, 1 u64; HANDOFF: the direction; 0 elsewhere
+  uint32_t where;           // HANDOFF: GM_HOSTSYNC_WHERE_*; 0 elsewhere
+  uint32_t pad;
+} gm_hostsync_record_t;
+
+typedef struct gm_hostsync_inject {
+  uint32_t test;            // one GM_HOSTSYNC_* bit
+  uint32_t kind;            // ADD: the kind 0..1; HANDOFF: the direction 0..1; ignored elsewhere
+  uint32_t a, b;            // g, s or block, round
+  uint32_t word;            // HANDOFF: payload word < 1024 lines
+  uint32_t mask;            // nonzero except for TICKET
+} gm_hostsync_inject_t;
+
+typedef struct gm_hostsync_dir {
+  uint64_t handoffs, observed, unseen, stale_words;
+  double poll_max_us;       // of observed hand-offs
+} gm_hostsync_dir_t;
+
+typedef struct gm_hostsync_result {
+  uint32_t tests_run;       // mask of the tests that ran to their end
+  uint32_t tests_skipped;   // asked for and not launched: atomics_supported is 0
+  uint32_t atomics_supported;
+  uint32_t blocks, host_threads, iters, spread, rounds, lines, budget_us, host_budget_us;
+  uint32_t cas_width;       // the CAS table's words
+  uint64_t words_in_error;  // ADD and CAS tables together
+  uint64_t add_u32_errors, add_u64_errors, cas_errors;
+  uint64_t tickets, holes, duplicates, counter_errors, out_of_range;
+  uint64_t swaps, swap_missing, swap_duplicates, swap_foreign;
+  uint64_t cas_giveups;
+  uint64_t host_ops_in_flight;
+  uint64_t lost_words;
+  gm_hostsync_dir_t dir[2];  // 0: host to device (seen by the kernel), 1: device to host
+  double rtt_median_us, rtt_max_us;
+  double ms[5];             // wall time of each test's launches: ADD, TICKET, SWAP, CAS, HANDOFF
+  uint32_t records_filled;  // <= GM_HOSTSYNC_MAX_RECORDS; later errors are counted only
+  uint32_t pad;
+  gm_hostsync_record_t records[GM_HOSTSYNC_MAX_RECORDS];
+  double seconds;           // wall time of the whole call
+} gm_hostsync_result_t;
+
+// The host's expectation for B = blocks + host_threads blocks. kind 0, 1 (ADD), 10 (TICKET: N_k),
+// 11 (CAS) and 13 (operations per word): the atomics test's table of `width` words (8 bytes for
+// kinds 1 and 11, else 4). kind 14 (swap): B * 256 * iters uint64, word << 32 | token of
+// operation g * iters + s. out_bytes must say exactly that. Host only, needs no GPU.
+int gm_probe_hostsync_expected(uint32_t kind, uint32_t blocks, uint32_t host_threads,
+                               uint32_t iters, uint32_t width, uint64_t seed, void* out,
+                               uint64_t out_bytes);
+// The CAS table's width for a requested spread. Host only.
+int gm_probe_hostsync_cas_width(uint32_t blocks, uint32_t host_threads, uint32_t iters,
+                                uint32_t spread, uint32_t* width);
+// E(dir, b, r, word) of the hand-off. Host only.
+uint32_t gm_probe_hostsync_payload(uint64_t seed, uint32_t dir, uint32_t block, uint32_t round,
+                                   uint32_t word);
+// hipDeviceAttributeHostNativeAtomicSupported of device `dev`.
+int gm_probe_hostsync_supported(int dev, int* supported);
+// One test on the current device with its own pinned memory, on `stream` (may be NULL); each
+// waits for its launch and its host threads and sets its own fields of *out. Bad arguments
+// (geometry, a width that breaks the CAS cap, an injection outside the run): hipErrorInvalidValue
+// before any HIP call; blocks above the CU count: the same, once the device has been asked.
+// table_out (may be NULL) takes the final table: `width` words of 4 bytes, 8 for kind 1 and cas.
+int gm_probe_hostsync_add(uint32_t kind, uint32_t blocks, uint32_t host_threads, uint32_t iters,
+                          uint32_t width, uint64_t seed, const gm_hostsync_inject_t* inject,
+                          void* stream, void* table_out, gm_hostsync_result_t* out);
+int gm_probe_hostsync_ticket(uint32_t blocks, uint32_t host_threads, uint32_t iters,
+                             uint32_t counters, uint64_t seed, const gm_hostsync_inject_t* inject,
+                             void* stream, gm_hostsync_result_t* out);
+int gm_probe_hostsync_swap(uint32_t blocks, uint32_t host_threads, uint32_t iters, uint32_t width,
+                           uint64_t seed, const gm_hostsync_inject_t* inject, void* stream,
+                           gm_hostsync_result_t* out);
+int gm_probe_hostsync_cas(uint32_t blocks, uint32_t host_threads, uint32_t iters, uint32_t width,
+                          uint64_t seed, const gm_hostsync_inject_t* inject, void* stream,
+                          void* table_out, gm_hostsync_result_t* out);
+int gm_probe_hostsync_handoff(uint32_t blocks, uint32_t host_threads, uint32_t rounds,
+                              uint32_t lines, uint32_t budget_us, uint32_t host_budget_us,
+                              uint64_t seed, const gm_hostsync_inject_t* inject, void* stream,
+                              gm_hostsync_result_t* out);
+// The driver: the tests of tests_mask on device `dev` with its own buffers and stream. blocks = 0:
+// min(16, multiProcessorCount). `inject` (may be NULL) must name a test of tests_mask that is run
+// and a place inside the run. The hand-off needs host_threads >= 1. Bad arguments:
+// hipErrorInvalidValue before any HIP call (what depends on the CU count is checked once the
+// device has been asked).
+int gm_probe_hostsync(int dev, uint32_t tests_mask, uint32_t blocks, uint32_t host_threads,
+                      uint32_t iters, uint32_t spread, uint32_t rounds, uint32_t lines,
+                      uint32_t budget_us, uint32_t host_budget_us, uint64_t seed,
+                      const gm_hostsync_inject_t* inject, gm_hostsync_result_t* out);
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(gm_hostsync_record_t) == 40 && sizeof(gm_hostsync_inject_t) == 24 &&
+                  sizeof(gm_hostsync_dir_t) == 40 && sizeof(gm_hostsync_result_t) == 968,
+              "gm_hostsync_* layout");
+static_assert(__builtin_offsetof(gm_hostsync_result_t, words_in_error) == 48 &&
+                  __builtin_offsetof(gm_hostsync_result_t, tickets) == 80 &&
+                  __builtin_offsetof(gm_hostsync_result_t, swaps) == 120 &&
+                  __builtin_offsetof(gm_hostsync_result_t, cas_giveups) == 152 &&
+                  __builtin_offsetof(gm_hostsync_result_t, dir) == 176 &&
+                  __builtin_offsetof(gm_hostsync_result_t, rtt_median_us) == 256 &&
+                  __builtin_offsetof(gm_hostsync_result_t, ms) == 272 &&
+                  __builtin_offsetof(gm_hostsync_result_t, records) == 320 &&
+                  __builtin_offsetof(gm_hostsync_result_t, seconds) == 960,
+              "gm_hostsync_result_t layout");
 static_assert(sizeof(gm_atomics_kind_t) == 40 && sizeof(gm_atomics_record_t) == 40 &&
                   sizeof(gm_atomics_inject_t) == 24 && sizeof(gm_atomics_result_t) == 3448,
               "gm_atomics_* layout");
