@@ -25,9 +25,10 @@ No silent fallback: a missing ``libgm_probe.so`` or a HIP failure raises.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Iterable, Optional, Tuple
+from typing import Dict, Optional
 
 from gpumounter_amd import _native
+from gpumounter_amd.ops._testargs import Checks
 from gpumounter_amd.ops.probe import ProbeError, _check
 
 TESTS = {"add": 1, "ticket": 2, "cas": 4, "handoff": 8}
@@ -57,44 +58,9 @@ ERROR_COUNTERS = ("words_in_error", "holes", "duplicates", "counter_errors", "or
                   "out_of_range", "cas_giveups", "stale_words", "lost_words")
 
 
-def _int(v, lo: int, hi: int, what: str) -> int:
-    if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
-        raise ProbeError(f"atomics: {what} must be an integer in [{lo}, {hi}], got {v!r}")
-    return v
-
-
-def _pow2(v, hi: int, what: str) -> int:
-    _int(v, 1, hi, what)
-    if v & (v - 1):
-        raise ProbeError(f"atomics: {what} must be a power of two, got {v}")
-    return v
-
-
-def bit_of(test) -> int:
-    """The bit of one test, given by name or by bit."""
-    if isinstance(test, str) and test in TESTS:
-        return TESTS[test]
-    if isinstance(test, int) and not isinstance(test, bool) and test in TEST_NAMES:
-        return test
-    raise ProbeError(f"unknown atomics test {test!r} (one of {', '.join(TESTS)})")
-
-
-def mask_of(tests: Iterable) -> int:
-    if isinstance(tests, (str, int)):
-        tests = (tests,)
-    mask = 0
-    for t in tests:
-        mask |= bit_of(t)
-    if not mask:
-        raise ProbeError("atomics needs at least one test")
-    return mask
-
-
-def parse_tests(text) -> Tuple[str, ...]:
-    """``"add,ticket,cas,handoff"`` → ("add", "ticket", "cas", "handoff"); every name is checked."""
-    names = tuple(t.strip() for t in str(text).split(",") if t.strip())
-    mask_of(names)
-    return names
+_checks = Checks("atomics", TESTS)
+_int, _pow2 = _checks.int_in, _checks.pow2
+bit_of, mask_of, parse_tests = _checks.bit_of, _checks.mask_of, _checks.parse_tests
 
 
 def kind_of(kind) -> int:

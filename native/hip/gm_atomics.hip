@@ -3,30 +3,26 @@
 // and does the documented agent-scope release/acquire hand-off deliver every word?
 //
 // Formulas and the contract are in gm_probe.h, the value functions and the host reference in
-// gm_atomics_ref.h. No kernel here waits without a bound on another block: the known-answer
-// kernels (k_add, k_ticket) do not wait, k_cas bounds its retries by the host's count of
-// operations into the word, and k_handoff polls for at most budget_us of wall_clock64() and books
-// "not seen" as a legal outcome. So a call ends on any device state, blocks run one after another
-// included. Every index is masked or checked against its table before it is used.
+// gm_atomics_ref.h, the per-step operations in gm_atomics_steps.h (here at agent scope) and the
+// hand-off's pieces in gm_atomics_dev.h. No kernel here waits without a bound on another block:
+// the known-answer kernels (k_add, k_ticket) do not wait, k_cas bounds its retries by the host's
+// count of operations into the word, and k_handoff polls for at most budget_us of wall_clock64()
+// and books "not seen" as a legal outcome. So a call ends on any device state, blocks run one
+// after another included. Every index is masked or checked against its table before it is used.
 #include "gm_probe.h"
 
-#include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <vector>
 
-#include "gm_atomics_ref.h"
-#include "gm_probe_common.h"
+#include "gm_atomics_dev.h"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-#define GM_RLX __ATOMIC_RELAXED
 #define GM_AGENT __HIP_MEMORY_SCOPE_AGENT
+typedef DevOps<GM_AGENT> Ops;
+typedef gm_atomics_inj_t Inj;
 
-constexpr int kThreads = GM_ATOMICS_THREADS;
 // s_getreg immediate: (size - 1) << 11 | offset << 6 | register; XCC_ID[3:0] of register 20
 constexpr int kGetXcc = ((4 - 1) << 11) | (0 << 6) | 20;
 
@@ -37,10 +33,6 @@ struct DevTab {
   uint32_t pairs_observed[256], pairs_stale[256], xcc_blocks[16];
   uint32_t claims, pad;
   gm_atomics_record_t rec[GM_ATOMICS_MAX_RECORDS];
-};
-
-struct Inj {
-  uint32_t a, b, word, mask, on;  // on 0: none
 };
 
 // Cold: entered per error only.
@@ -67,56 +59,8 @@ __global__ __launch_bounds__(kThreads) void k_census(DevTab* tab) {
 __global__ __launch_bounds__(kThreads) void k_add(uint32_t kind, void* table, uint32_t width,
                                                   uint32_t iters, uint64_t seed, Inj inj) {
   const uint32_t g = blockIdx.x * kThreads + threadIdx.x;
-  uint32_t* t32 = (uint32_t*)table;
-  uint64_t* t64 = (uint64_t*)table;
-  for (uint32_t s = 0; s < iters; ++s) {
-    uint32_t h = gm_atomics_hash(seed, kind, 0, g, s);
-    if (inj.on && g == inj.a && s == inj.b) h ^= inj.mask;
-    const uint32_t w = gm_atomics_addr(g, s, width);
-    switch (kind) {
-      case GM_ATOMICS_K_ADD_U32:
-        (void)__hip_atomic_fetch_add(&t32[w], h, GM_RLX, GM_AGENT);
-        break;
-      case GM_ATOMICS_K_ADD_U64:
-        (void)__hip_atomic_fetch_add(&t64[w], gm_atomics_op64(seed, kind, h, g, s), GM_RLX,
-                                     GM_AGENT);
-        break;
-      case GM_ATOMICS_K_XOR_U64:
-        (void)__hip_atomic_fetch_xor(&t64[w], gm_atomics_op64(seed, kind, h, g, s), GM_RLX,
-                                     GM_AGENT);
-        break;
-      case GM_ATOMICS_K_UMAX_U32:
-        (void)__hip_atomic_fetch_max(&t32[w], h, GM_RLX, GM_AGENT);
-        break;
-      case GM_ATOMICS_K_UMIN_U32:
-        (void)__hip_atomic_fetch_min(&t32[w], h, GM_RLX, GM_AGENT);
-        break;
-      case GM_ATOMICS_K_AND_U32:
-        (void)__hip_atomic_fetch_and(&t32[w], ~gm_atomics_bit(h), GM_RLX, GM_AGENT);
-        break;
-      case GM_ATOMICS_K_OR_U32:
-        (void)__hip_atomic_fetch_or(&t32[w], gm_atomics_bit(h), GM_RLX, GM_AGENT);
-        break;
-      case GM_ATOMICS_K_ADD_F32:
-        (void)__hip_atomic_fetch_add((float*)&t32[w], (float)gm_atomics_small(h), GM_RLX,
-                                     GM_AGENT);
-        break;
-      case GM_ATOMICS_K_ADD_F64:
-        (void)__hip_atomic_fetch_add((double*)&t64[w], (double)gm_atomics_small(h), GM_RLX,
-                                     GM_AGENT);
-        break;
-      case GM_ATOMICS_K_PK_ADD_BF16: {
-        bf16x2 v;
-        v[0] = (__bf16)(float)(h & 1u);
-        v[1] = (__bf16)(float)((h >> 1) & 1u);
-        (void)__builtin_amdgcn_global_atomic_fadd_v2bf16(
-            (__attribute__((address_space(1))) bf16x2*)&t32[w], v);
-        break;
-      }
-      default:
-        break;
-    }
-  }
+  for (uint32_t s = 0; s < iters; ++s)
+    gm_atomics_add_step<Ops>(kind, table, width, seed, inj, g, s);
 }
 
 // ---- compare after the kernel boundary: table against the host's, words of 4 or 8 bytes
@@ -133,29 +77,16 @@ __global__ __launch_bounds__(kThreads) void k_compare(const void* table, const v
   }
 }
 
-// ---- CAS: add u64 through a compare-exchange loop. Every failed exchange means another thread's
-// succeeded, and bound[w] operations go into word w in all, so a correct machine cannot fail
-// bound[w] times: the loop ends after at most that many rounds whatever the device does.
+// ---- CAS: the step's loop, bounded by the host's count of operations into the word
 __global__ __launch_bounds__(kThreads) void k_cas(uint64_t* table, const uint32_t* bound,
                                                   uint32_t width, uint32_t iters, uint64_t seed,
                                                   Inj inj, DevTab* tab) {
   const uint32_t g = blockIdx.x * kThreads + threadIdx.x;
-  for (uint32_t s = 0; s < iters; ++s) {
-    uint32_t h = gm_atomics_hash(seed, GM_ATOMICS_K_CAS, 0, g, s);
-    if (inj.on && g == inj.a && s == inj.b) h ^= inj.mask;
-    const uint64_t op = gm_atomics_op64(seed, GM_ATOMICS_K_CAS, h, g, s);
-    const uint32_t w = gm_atomics_addr(g, s, width);
-    const uint32_t limit = bound[w];
-    uint64_t old = __hip_atomic_load(&table[w], GM_RLX, GM_AGENT);
-    uint32_t fails = 0;
-    while (!__hip_atomic_compare_exchange_strong(&table[w], &old, old + op, GM_RLX, GM_RLX,
-                                                 GM_AGENT)) {
-      if (++fails >= limit) {
-        atomicAdd(&tab->giveups, 1ull);
-        return;
-      }
+  for (uint32_t s = 0; s < iters; ++s)
+    if (!gm_atomics_cas_step<Ops>(table, bound, width, seed, inj, g, s)) {
+      atomicAdd(&tab->giveups, 1ull);
+      return;
     }
-  }
 }
 
 // ---- TICKET: returning fetch-add; off[k] .. off[k + 1] are counter k's marks
@@ -168,12 +99,10 @@ __global__ __launch_bounds__(kThreads) void k_ticket(uint32_t* ctr, const uint64
 #pragma unroll
   for (int i = 0; i < 16; ++i) last[i] = 0;
   for (uint32_t s = 0; s < iters; ++s) {
-    const uint32_t d = gm_atomics_draw(gm_atomics_hash(seed, GM_ATOMICS_K_TICKET, 0, g, s));
-    const uint32_t k = gm_atomics_addr(g, s, counters);
-    const uint64_t base = off[k];
-    // N_k, and never past the end of the marks whatever off[] holds
-    const uint64_t room = base < n_marks && off[k + 1] - base <= n_marks - base ? off[k + 1] - base : 0;
-    const uint32_t old = __hip_atomic_fetch_add(&ctr[k], d, GM_RLX, GM_AGENT);
+    uint32_t old, d;
+    const uint32_t out_of_range = gm_atomics_ticket_step<Ops>(ctr, off, marks, n_marks, counters,
+                                                              seed, inj, g, s, old, d);
+    if (out_of_range) atomicAdd(&tab->out_of_range, (unsigned long long)out_of_range);
     if (counters <= 16) {  // slot s mod K is this counter's: the thread was here K draws ago
       const uint32_t slot = s & (counters - 1u);
       uint32_t prev = 0;
@@ -185,15 +114,6 @@ __global__ __launch_bounds__(kThreads) void k_ticket(uint32_t* ctr, const uint64
         }
       if (s >= counters && old < prev) atomicAdd(&tab->order_violations, 1ull);
     }
-    for (uint32_t i = 0; i < d; ++i) {
-      const uint64_t ticket = (uint64_t)old + i;
-      if (ticket < room)
-        (void)__hip_atomic_fetch_add(&marks[base + ticket], 1u, GM_RLX, GM_AGENT);
-      else
-        atomicAdd(&tab->out_of_range, 1ull);
-    }
-    if (inj.on && g == inj.a && s == inj.b && old < room)
-      (void)__hip_atomic_fetch_add(&marks[base + old], 1u, GM_RLX, GM_AGENT);
   }
 }
 
@@ -234,42 +154,20 @@ __global__ __launch_bounds__(kThreads) void k_handoff(HandoffArgs a, DevTab* tab
   const uint32_t xcc = __builtin_amdgcn_s_getreg(kGetXcc) & 15u;
   const uint32_t box_words = a.lines * GM_ATOMICS_LINE_WORDS;
   for (uint32_t r = 0; r < a.rounds; ++r) {
-    // 1. produce the own mailbox, the form MI355X documents as valid: plain stores, every wave
-    // drains them, barrier, then one lane releases at agent scope and stores the flag
+    // 1. produce the own mailbox and release its flag at agent scope
     const uint32_t mine = b * a.rounds + r;
-    u32x4* dst = (u32x4*)(a.payload + (size_t)mine * box_words);
-    for (uint32_t l = 0; l < a.lines; ++l) {
-      const uint32_t word = l * GM_ATOMICS_LINE_WORDS + 4 * t;
-      uint32_t v[4];
-#pragma unroll
-      for (uint32_t i = 0; i < 4; ++i) {
-        v[i] = gm_atomics_payload(a.seed, b, r, word + i);
-        if (a.inj.on && b == a.inj.a && r == a.inj.b && word + i == a.inj.word) v[i] ^= a.inj.mask;
-      }
-      const u32x4 q = {v[0], v[1], v[2], v[3]};
-      dst[l * kThreads + t] = q;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      // the compiler may drop the fence's own wait when it can prove the counter empty
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&a.flags[(size_t)mine * GM_ATOMICS_FLAG_WORDS], (xcc << 16) | (r + 1u),
-                         GM_RLX, GM_AGENT);
-    }
+    const bool hit = gm_atomics_inj_hit(a.inj, b, r);
+    store_box(a.payload + (size_t)mine * box_words, a.lines, [&](uint32_t word) {
+      const uint32_t v = gm_atomics_payload(a.seed, b, r, word);
+      return hit && word == a.inj.word ? v ^ a.inj.mask : v;
+    });
+    release_flag<GM_AGENT>(&a.flags[(size_t)mine * GM_ATOMICS_FLAG_WORDS], (xcc << 16) | (r + 1u));
 
-    // 2. consume the partner's: first pull its lines into this CU's L1 with plain loads, so that
-    // a missing invalidate shows (an L1-cold reader would read fresh bytes and hide it)
+    // 2. consume the partner's, L1-warm
     const uint32_t p = gm_atomics_partner(b, r, G);
     const uint32_t theirs = p * a.rounds + r;
-    const u32x4* src = (const u32x4*)(a.payload + (size_t)theirs * box_words);
-    uint32_t sink = 0;
-    for (uint32_t l = 0; l < a.lines; ++l) {
-      const u32x4 q = src[l * kThreads + t];
-      sink ^= q.x ^ q.y ^ q.z ^ q.w;
-    }
-    asm volatile("" ::"v"(sink) : "memory");
+    const uint32_t* src = a.payload + (size_t)theirs * box_words;
+    warm_box(src, a.lines);
     if (t == 0) {
       const uint32_t* flag = &a.flags[(size_t)theirs * GM_ATOMICS_FLAG_WORDS];
       const uint64_t t0 = wall_clock64();
@@ -302,23 +200,15 @@ __global__ __launch_bounds__(kThreads) void k_handoff(HandoffArgs a, DevTab* tab
     }
     __syncthreads();
     const uint32_t seen = lds[0], px = (lds[1] >> 16) & 15u;
-    if (seen) {
-      for (uint32_t l = 0; l < a.lines; ++l) {
-        const u32x4 q = src[l * kThreads + t];
-        const uint32_t got[4] = {q.x, q.y, q.z, q.w};
-        const uint32_t word = l * GM_ATOMICS_LINE_WORDS + 4 * t;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-          const uint32_t e = gm_atomics_payload(a.seed, p, r, word + i);
-          if (got[i] != e) {
+    if (seen)
+      compare_box(
+          src, a.lines, [&](uint32_t word) { return gm_atomics_payload(a.seed, p, r, word); },
+          [&](uint32_t word, uint32_t e, uint32_t got) {
             atomicAdd(&tab->stale, 1ull);
             atomicAdd(&tab->pairs_stale[px * 16 + xcc], 1u);
-            report(tab, GM_ATOMICS_HANDOFF, GM_ATOMICS_K_HANDOFF,
-                   ((uint64_t)theirs << 14) | (word + i), e, got[i], px, xcc);
-          }
-        }
-      }
-    }
+            report(tab, GM_ATOMICS_HANDOFF, GM_ATOMICS_K_HANDOFF, ((uint64_t)theirs << 14) | word,
+                   e, got, px, xcc);
+          });
     __syncthreads();  // lds[] is rewritten in the next round
   }
 }
@@ -327,23 +217,15 @@ __global__ __launch_bounds__(kThreads) void k_handoff(HandoffArgs a, DevTab* tab
 __global__ __launch_bounds__(kThreads) void k_handoff_audit(HandoffArgs a, DevTab* tab) {
   const uint32_t t = threadIdx.x, m = blockIdx.x;
   const uint32_t b = m / a.rounds, r = m % a.rounds;
-  const uint32_t box_words = a.lines * GM_ATOMICS_LINE_WORDS;
   const uint32_t f = a.flags[(size_t)m * GM_ATOMICS_FLAG_WORDS];
-  const u32x4* src = (const u32x4*)(a.payload + (size_t)m * box_words);
-  for (uint32_t l = 0; l < a.lines; ++l) {
-    const u32x4 q = src[l * kThreads + t];
-    const uint32_t got[4] = {q.x, q.y, q.z, q.w};
-    const uint32_t word = l * GM_ATOMICS_LINE_WORDS + 4 * t;
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) {
-      const uint32_t e = gm_atomics_payload(a.seed, b, r, word + i);
-      if (got[i] != e) {
+  compare_box(
+      a.payload + (size_t)m * a.lines * GM_ATOMICS_LINE_WORDS, a.lines,
+      [&](uint32_t word) { return gm_atomics_payload(a.seed, b, r, word); },
+      [&](uint32_t word, uint32_t e, uint32_t got) {
         atomicAdd(&tab->lost, 1ull);
-        report(tab, GM_ATOMICS_HANDOFF, GM_ATOMICS_K_HANDOFF, ((uint64_t)m << 14) | (word + i), e,
-               got[i], (f >> 16) & 15u, GM_ATOMICS_XCC_UNKNOWN);
-      }
-    }
-  }
+        report(tab, GM_ATOMICS_HANDOFF, GM_ATOMICS_K_HANDOFF, ((uint64_t)m << 14) | word, e, got,
+               (f >> 16) & 15u, GM_ATOMICS_XCC_UNKNOWN);
+      });
   if (t == 0 && (f & 0xFFFFu) != r + 1u) {
     atomicAdd(&tab->lost, 1ull);
     report(tab, GM_ATOMICS_HANDOFF, GM_ATOMICS_K_HANDOFF, (1ull << 40) | m, r + 1u,
@@ -373,22 +255,7 @@ bool inject_ok(const gm_atomics_inject_t* in, uint32_t test, uint32_t blocks, ui
   if (test == GM_ATOMICS_HANDOFF)
     return in->a < blocks && in->b < rounds && in->word < lines * GM_ATOMICS_LINE_WORDS &&
            in->mask != 0;
-  if (in->a >= blocks * (uint32_t)kThreads || in->b >= iters) return false;
-  if (test == GM_ATOMICS_TICKET) return true;
-  if (test == GM_ATOMICS_ADD && in->kind >= GM_ATOMICS_ADD_KINDS) return false;
-  return in->mask != 0;
-}
-
-Inj inj_for(const gm_atomics_inject_t* in, uint32_t test, uint32_t kind) {
-  Inj j{};
-  if (in && in->test == test && (test != GM_ATOMICS_ADD || in->kind == kind)) {
-    j.a = in->a;
-    j.b = in->b;
-    j.word = in->word;
-    j.mask = in->mask;
-    j.on = 1;
-  }
-  return j;
+  return inject_step_ok(in, test, blocks * (uint32_t)kThreads, iters, GM_ATOMICS_ADD_KINDS);
 }
 
 unsigned grid_for(uint64_t n) {
@@ -460,18 +327,6 @@ int launch_handoff(void* payload, void* flags, uint32_t blocks, uint32_t rounds,
   return (int)hipGetLastError();
 }
 
-// wall_clock64() ticks in budget_us on the current device
-int budget_ticks_of(uint32_t budget_us, double* ticks_per_us, uint64_t* ticks) {
-  int dev = 0, khz = 0;
-  GM_CHECK(hipGetDevice(&dev));
-  GM_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-  if (khz <= 0) return (int)hipErrorInvalidDevice;
-  *ticks_per_us = khz / 1000.0;
-  *ticks = (uint64_t)(budget_us * *ticks_per_us + 0.5);
-  if (*ticks == 0) *ticks = 1;
-  return 0;
-}
-
 void fill_result(const DevTab& h, double ticks_per_us, gm_atomics_result_t* out) {
   for (int k = 0; k < GM_ATOMICS_NKINDS; ++k) {
     out->kinds[k].words_in_error = h.words_bad[k];
@@ -505,22 +360,12 @@ void fill_result(const DevTab& h, double ticks_per_us, gm_atomics_result_t* out)
   for (uint32_t i = 0; i < out->records_filled; ++i) out->records[i] = h.rec[i];
 }
 
-// a zeroed table on the stream's device, read back after the stream has drained
-struct Tab {
-  DevBuf buf;
-  DevTab* dev() const { return (DevTab*)buf.p; }
-  hipError_t create(hipStream_t st) {
-    const hipError_t e = buf.alloc(sizeof(DevTab));
-    return e != hipSuccess ? e : hipMemsetAsync(buf.p, 0, sizeof(DevTab), st);
-  }
-  int read(hipStream_t st, double ticks_per_us, gm_atomics_result_t* out) {
-    GM_CHECK(hipStreamSynchronize(st));
-    std::vector<unsigned char> raw(sizeof(DevTab));
-    GM_CHECK(hipMemcpy(raw.data(), buf.p, sizeof(DevTab), hipMemcpyDeviceToHost));
-    fill_result(*(const DevTab*)raw.data(), ticks_per_us, out);
-    return 0;
-  }
-};
+// the table's counters into the result, after the stream has drained
+int read_result(Tab<DevTab>& tab, hipStream_t st, double ticks_per_us, gm_atomics_result_t* out) {
+  if (int e = tab.read(st)) return e;
+  fill_result(tab.host, ticks_per_us, out);
+  return 0;
+}
 
 void set_kind(gm_atomics_kind_t* k, uint64_t ops, uint32_t width, double ms) {
   k->ops = ops;
@@ -586,12 +431,12 @@ int gm_probe_atomics_cas(void* dev_table, const void* dev_bounds, uint32_t width
       (inject && !inject_ok(inject, GM_ATOMICS_CAS, blocks, iters, 0, 0)))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  Tab tab;
-  GM_CHECK(tab.create(st));
+  Tab<DevTab> tab;
+  if (int e = tab.create(st)) return e;
   if (int e = launch_cas(dev_table, dev_bounds, width, blocks, iters, seed,
                          inj_for(inject, GM_ATOMICS_CAS, 0), st, tab.dev(), nullptr))
     return e;
-  return tab.read(st, 0, out);
+  return read_result(tab, st, 0, out);
 }
 
 int gm_probe_atomics_ticket(void* dev_ctr, const void* dev_off, void* dev_marks, uint64_t marks,
@@ -608,13 +453,13 @@ int gm_probe_atomics_ticket(void* dev_ctr, const void* dev_off, void* dev_marks,
       marks > 4 * ops || (inject && !inject_ok(inject, GM_ATOMICS_TICKET, blocks, iters, 0, 0)))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  Tab tab;
-  GM_CHECK(tab.create(st));
+  Tab<DevTab> tab;
+  if (int e = tab.create(st)) return e;
   if (int e = launch_ticket(dev_ctr, dev_off, dev_marks, marks, counters, blocks, iters, seed,
                             inj_for(inject, GM_ATOMICS_TICKET, 0), st, tab.dev(), nullptr))
     return e;
   out->tickets = ops;
-  return tab.read(st, 0, out);
+  return read_result(tab, st, 0, out);
 }
 
 int gm_probe_atomics_handoff(void* dev_payload, void* dev_flags, uint32_t blocks, uint32_t rounds,
@@ -631,12 +476,12 @@ int gm_probe_atomics_handoff(void* dev_payload, void* dev_flags, uint32_t blocks
   double per_us = 0;
   uint64_t ticks = 0;
   if (int e = budget_ticks_of(budget_us, &per_us, &ticks)) return e;
-  Tab tab;
-  GM_CHECK(tab.create(st));
+  Tab<DevTab> tab;
+  if (int e = tab.create(st)) return e;
   if (int e = launch_handoff(dev_payload, dev_flags, blocks, rounds, lines, ticks, seed,
                              inj_for(inject, GM_ATOMICS_HANDOFF, 0), st, tab.dev(), nullptr))
     return e;
-  return tab.read(st, per_us, out);
+  return read_result(tab, st, per_us, out);
 }
 
 int gm_probe_atomics(int dev, uint32_t tests_mask, uint32_t blocks, uint32_t iters,
@@ -679,8 +524,8 @@ int gm_probe_atomics(int dev, uint32_t tests_mask, uint32_t blocks, uint32_t ite
   if (int e = budget_ticks_of(budget_us, &per_us, &ticks)) return e;
 
   hipStream_t st = nullptr;
-  Tab tab;
-  GM_CHECK(tab.create(st));
+  Tab<DevTab> tab;
+  if (int e = tab.create(st)) return e;
   Events ev[GM_ATOMICS_NKINDS];
   bool timed[GM_ATOMICS_NKINDS] = {};
   hipLaunchKernelGGL(k_census, dim3(blocks), dim3(kThreads), 0, st, tab.dev());
@@ -773,7 +618,7 @@ int gm_probe_atomics(int dev, uint32_t tests_mask, uint32_t blocks, uint32_t ite
     out->tests_run |= GM_ATOMICS_HANDOFF;
   }
 
-  if (int e = tab.read(st, per_us, out)) return e;
+  if (int e = read_result(tab, st, per_us, out)) return e;
   for (uint32_t k = 0; k < GM_ATOMICS_NKINDS; ++k)
     if (timed[k]) {
       float ms = 0;  // a pair that cannot be read books no time; the counts stand

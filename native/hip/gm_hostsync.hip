@@ -4,33 +4,30 @@
 // payload word, in both directions, while the kernel runs?
 //
 // Formulas and the contract are in gm_probe.h, the value functions and audits in
-// gm_hostsync_ref.h, the host threads' side in gm_hostsync_host.h. Every shared word lies in
-// PinnedBuf memory (mapped, coherent) and the kernels reach it through hipHostGetDevicePointer.
-// No kernel and no host thread waits without a bound: the known-answer kernels do not wait, the
-// CAS loops are bounded by the host's count of operations into the word, the kernel's flag poll
-// by budget_us of wall_clock64(), the host's by host_budget_us, and a host thread's start by
-// GM_HOSTSYNC_START_BOUND_US. Every index is masked or checked against its table before use.
+// gm_hostsync_ref.h, the host threads' side in gm_hostsync_host.h, the per-step operations in
+// gm_atomics_steps.h (here at system scope) and the hand-off's pieces in gm_atomics_dev.h. Every
+// shared word lies in PinnedBuf memory (mapped, coherent) and the kernels reach it through
+// hipHostGetDevicePointer. No kernel and no host thread waits without a bound: the known-answer
+// kernels do not wait, the CAS loops are bounded by the host's count of operations into the word,
+// the kernel's flag poll by budget_us of wall_clock64(), the host's by host_budget_us, and a host
+// thread's start by GM_HOSTSYNC_START_BOUND_US. Every index is masked or checked against its
+// table before use.
 #include "gm_probe.h"
 
-#include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <algorithm>
 #include <thread>
 #include <vector>
 
+#include "gm_atomics_dev.h"
 #include "gm_hostsync_host.h"
-#include "gm_hostsync_ref.h"
-#include "gm_probe_common.h"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-#define GM_RLX __ATOMIC_RELAXED
 #define GM_SYS __HIP_MEMORY_SCOPE_SYSTEM
-
-constexpr int kThreads = GM_HOSTSYNC_THREADS;
+typedef DevOps<GM_SYS> Ops;
+typedef gm_atomics_inj_t Inj;
 
 // the kernels' own counters, in device memory: nothing the host threads touch
 struct DevTab {
@@ -38,8 +35,6 @@ struct DevTab {
   uint32_t claims, pad;
   gm_hostsync_record_t rec[GM_HOSTSYNC_MAX_RECORDS];
 };
-
-typedef gm_hostsync_inj_t Inj;
 
 __device__ __forceinline__ void announce(uint32_t* ready) {
   if (threadIdx.x == 0) __hip_atomic_store(ready, 1u, GM_RLX, GM_SYS);
@@ -51,16 +46,8 @@ __global__ __launch_bounds__(kThreads) void k_add(uint32_t kind, void* table, ui
                                                   uint32_t* ready) {
   announce(ready);
   const uint32_t g = blockIdx.x * kThreads + threadIdx.x;
-  for (uint32_t s = 0; s < iters; ++s) {
-    uint32_t h = gm_atomics_hash(seed, kind, 0, g, s);
-    if (inj.on && g == inj.a && s == inj.b) h ^= inj.mask;
-    const uint32_t w = gm_atomics_addr(g, s, width);
-    if (kind == GM_ATOMICS_K_ADD_U64)
-      (void)__hip_atomic_fetch_add(&((uint64_t*)table)[w], gm_atomics_op64(seed, kind, h, g, s),
-                                   GM_RLX, GM_SYS);
-    else
-      (void)__hip_atomic_fetch_add(&((uint32_t*)table)[w], h, GM_RLX, GM_SYS);
-  }
+  for (uint32_t s = 0; s < iters; ++s)
+    gm_atomics_add_step<Ops>(kind, table, width, seed, inj, g, s);
 }
 
 // ---- TICKET: returning fetch-add; off[k] .. off[k + 1] are counter k's marks
@@ -72,22 +59,10 @@ __global__ __launch_bounds__(kThreads) void k_ticket(uint32_t* ctr, const uint64
   announce(ready);
   const uint32_t g = blockIdx.x * kThreads + threadIdx.x;
   for (uint32_t s = 0; s < iters; ++s) {
-    const uint32_t d = gm_atomics_draw(gm_atomics_hash(seed, GM_ATOMICS_K_TICKET, 0, g, s));
-    const uint32_t k = gm_atomics_addr(g, s, counters);
-    const uint64_t base = off[k];
-    // N_k, and never past the end of the marks whatever off[] holds
-    const uint64_t room =
-        base < n_marks && off[k + 1] - base <= n_marks - base ? off[k + 1] - base : 0;
-    const uint32_t old = __hip_atomic_fetch_add(&ctr[k], d, GM_RLX, GM_SYS);
-    for (uint32_t i = 0; i < d; ++i) {
-      const uint64_t ticket = (uint64_t)old + i;
-      if (ticket < room)
-        (void)__hip_atomic_fetch_add(&marks[base + ticket], 1u, GM_RLX, GM_SYS);
-      else
-        atomicAdd(&tab->out_of_range, 1ull);
-    }
-    if (inj.on && g == inj.a && s == inj.b && old < room)
-      (void)__hip_atomic_fetch_add(&marks[base + old], 1u, GM_RLX, GM_SYS);
+    uint32_t old, d;
+    const uint32_t out_of_range = gm_atomics_ticket_step<Ops>(ctr, off, marks, n_marks, counters,
+                                                              seed, inj, g, s, old, d);
+    if (out_of_range) atomicAdd(&tab->out_of_range, (unsigned long long)out_of_range);
   }
 }
 
@@ -96,38 +71,21 @@ __global__ __launch_bounds__(kThreads) void k_swap(uint32_t* words, uint32_t wid
                                                    Inj inj, uint32_t* ready, uint32_t* returned) {
   announce(ready);
   const uint32_t g = blockIdx.x * kThreads + threadIdx.x;
-  for (uint32_t s = 0; s < iters; ++s) {
-    uint32_t token = gm_hostsync_token(g, s);
-    if (inj.on && g == inj.a && s == inj.b) token ^= inj.mask;
-    returned[(size_t)g * iters + s] =
-        __hip_atomic_exchange(&words[gm_atomics_addr(g, s, width)], token, GM_RLX, GM_SYS);
-  }
+  for (uint32_t s = 0; s < iters; ++s)
+    returned[(size_t)g * iters + s] = gm_hostsync_swap_step<Ops>(words, width, inj, g, s);
 }
 
-// ---- CAS: add u64 through a compare-exchange loop. Every failed exchange means that another
-// participant's succeeded, on the GPU or on the host, and bound[w] operations go into word w in
-// all: the loop ends after at most that many rounds whatever the device and the host do.
+// ---- CAS: the step's loop, bounded by the count of operations into the word, GPU's and host's
 __global__ __launch_bounds__(kThreads) void k_cas(uint64_t* table, const uint32_t* bound,
                                                   uint32_t width, uint32_t iters, uint64_t seed,
                                                   Inj inj, uint32_t* ready, DevTab* tab) {
   announce(ready);
   const uint32_t g = blockIdx.x * kThreads + threadIdx.x;
-  for (uint32_t s = 0; s < iters; ++s) {
-    uint32_t h = gm_atomics_hash(seed, GM_ATOMICS_K_CAS, 0, g, s);
-    if (inj.on && g == inj.a && s == inj.b) h ^= inj.mask;
-    const uint64_t op = gm_atomics_op64(seed, GM_ATOMICS_K_CAS, h, g, s);
-    const uint32_t w = gm_atomics_addr(g, s, width);
-    const uint32_t limit = bound[w];
-    uint64_t old = __hip_atomic_load(&table[w], GM_RLX, GM_SYS);
-    uint32_t fails = 0;
-    while (!__hip_atomic_compare_exchange_strong(&table[w], &old, old + op, GM_RLX, GM_RLX,
-                                                 GM_SYS)) {
-      if (++fails >= limit) {
-        atomicAdd(&tab->giveups, 1ull);
-        return;
-      }
+  for (uint32_t s = 0; s < iters; ++s)
+    if (!gm_atomics_cas_step<Ops>(table, bound, width, seed, inj, g, s)) {
+      atomicAdd(&tab->giveups, 1ull);
+      return;
     }
-  }
 }
 
 // ---- HANDOFF: mailbox m = b * rounds + r of either direction at word m * lines * 1024, its
@@ -146,15 +104,9 @@ __global__ __launch_bounds__(kThreads) void k_handoff(HandoffArgs a, DevTab* tab
   const uint32_t box_words = a.lines * GM_HOSTSYNC_LINE_WORDS;
   for (uint32_t r = 0; r < a.rounds; ++r) {
     const size_t m = (size_t)b * a.rounds + r;
-    // 2. consume the host's: first touch the payload with plain loads, so that bytes this CU may
-    // hold from before the flag show if the acquire does not drop them
-    const u32x4* src = (const u32x4*)(a.pay_h + m * box_words);
-    uint32_t sink = 0;
-    for (uint32_t l = 0; l < a.lines; ++l) {
-      const u32x4 q = src[l * kThreads + t];
-      sink ^= q.x ^ q.y ^ q.z ^ q.w;
-    }
-    asm volatile("" ::"v"(sink) : "memory");
+    // 2. consume the host's, L1-warm
+    const uint32_t* src = a.pay_h + m * box_words;
+    warm_box(src, a.lines);
     if (t == 0) {
       const uint32_t* flag = &a.flag_h[m * GM_HOSTSYNC_FLAG_WORDS];
       const uint64_t t0 = wall_clock64();
@@ -182,55 +134,30 @@ __global__ __launch_bounds__(kThreads) void k_handoff(HandoffArgs a, DevTab* tab
     }
     __syncthreads();
     const uint32_t seen = lds[0];
-    if (seen) {
-      for (uint32_t l = 0; l < a.lines; ++l) {
-        const u32x4 q = src[l * kThreads + t];
-        const uint32_t got[4] = {q.x, q.y, q.z, q.w};
-        const uint32_t word = l * GM_HOSTSYNC_LINE_WORDS + 4 * t;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-          const uint32_t e = gm_hostsync_payload(a.seed, 0, b, r, word + i);
-          if (got[i] != e) {
+    if (seen)
+      compare_box(
+          src, a.lines, [&](uint32_t word) { return gm_hostsync_payload(a.seed, 0, b, r, word); },
+          [&](uint32_t word, uint32_t e, uint32_t got) {
             atomicAdd(&tab->stale, 1ull);
             const unsigned int slot = atomicAdd(&tab->claims, 1u);
             if (slot < GM_HOSTSYNC_MAX_RECORDS) {
               gm_hostsync_record_t* rec = &tab->rec[slot];
-              rec->index = ((uint64_t)b << 20) | ((uint64_t)r << 14) | (word + i);
+              rec->index = ((uint64_t)b << 20) | ((uint64_t)r << 14) | word;
               rec->expected = e;
-              rec->got = got[i];
+              rec->got = got;
               rec->test = GM_HOSTSYNC_HANDOFF;
               rec->kind = 0;  // host to device
               rec->where = GM_HOSTSYNC_WHERE_STALE;
               rec->pad = 0;
             }
-          }
-        }
-      }
-    }
-    // 3. produce the reply: plain stores, every wave drains them, barrier, then one lane
-    // releases at system scope and stores the flag
-    u32x4* dst = (u32x4*)(a.pay_d + m * box_words);
-    for (uint32_t l = 0; l < a.lines; ++l) {
-      const uint32_t word = l * GM_HOSTSYNC_LINE_WORDS + 4 * t;
-      uint32_t v[4];
-#pragma unroll
-      for (uint32_t i = 0; i < 4; ++i) {
-        v[i] = gm_hostsync_payload(a.seed, 1, b, r, word + i);
-        if (a.inj.on && a.inj.dir == 1 && b == a.inj.a && r == a.inj.b && word + i == a.inj.word)
-          v[i] ^= a.inj.mask;
-      }
-      const u32x4 q = {v[0], v[1], v[2], v[3]};
-      dst[l * kThreads + t] = q;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-      // the compiler may drop the fence's own wait when it can prove the counter empty
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&a.flag_d[m * GM_HOSTSYNC_FLAG_WORDS], (seen << 16) | (r + 1u), GM_RLX,
-                         GM_SYS);
-    }
+          });
+    // 3. produce the reply and release its flag at system scope
+    const bool hit = a.inj.dir == 1 && gm_atomics_inj_hit(a.inj, b, r);
+    store_box(a.pay_d + m * box_words, a.lines, [&](uint32_t word) {
+      const uint32_t v = gm_hostsync_payload(a.seed, 1, b, r, word);
+      return hit && word == a.inj.word ? v ^ a.inj.mask : v;
+    });
+    release_flag<GM_SYS>(&a.flag_d[m * GM_HOSTSYNC_FLAG_WORDS], (seen << 16) | (r + 1u));
     __syncthreads();  // lds[] is rewritten in the next round
   }
 }
@@ -248,23 +175,7 @@ bool inject_ok(const gm_hostsync_inject_t* in, uint32_t test, uint32_t blocks,
   if (test == GM_HOSTSYNC_HANDOFF)
     return in->kind < 2 && in->a < blocks && in->b < rounds &&
            in->word < lines * GM_HOSTSYNC_LINE_WORDS && in->mask != 0;
-  if (in->a >= (blocks + host_threads) * (uint32_t)kThreads || in->b >= iters) return false;
-  if (test == GM_HOSTSYNC_TICKET) return true;
-  if (test == GM_HOSTSYNC_ADD && in->kind > GM_ATOMICS_K_ADD_U64) return false;
-  return in->mask != 0;
-}
-
-Inj inj_for(const gm_hostsync_inject_t* in, uint32_t test, uint32_t kind) {
-  Inj j;
-  if (in && in->test == test && (test != GM_HOSTSYNC_ADD || in->kind == kind)) {
-    j.a = in->a;
-    j.b = in->b;
-    j.word = in->word;
-    j.mask = in->mask;
-    j.dir = test == GM_HOSTSYNC_HANDOFF ? in->kind : 0;
-    j.on = 1;
-  }
-  return j;
+  return inject_step_ok(in, test, (blocks + host_threads) * (uint32_t)kThreads, iters, Ops::kKinds);
 }
 
 void add_record(gm_hostsync_result_t* out, uint32_t test, uint32_t kind, uint64_t index,
@@ -290,18 +201,6 @@ struct Shared {
     GM_CHECK(hipHostGetDevicePointer(&dev, buf.p, 0));
     return dev ? 0 : (int)hipErrorInvalidValue;
   }
-};
-
-// a zeroed table of the kernels' own counters, read back after the stream has drained
-struct Tab {
-  DevBuf buf;
-  DevTab host{};
-  DevTab* dev() const { return (DevTab*)buf.p; }
-  int create(hipStream_t st) {
-    GM_CHECK(buf.alloc(sizeof(DevTab)));
-    return (int)hipMemsetAsync(buf.p, 0, sizeof(DevTab), st);
-  }
-  int read() { return (int)hipMemcpy(&host, buf.p, sizeof(DevTab), hipMemcpyDeviceToHost); }
 };
 
 // the host threads of one launch, joined on every return path
@@ -412,7 +311,7 @@ int run_ticket(const Ctx& c, uint32_t counters) {
   const uint64_t n_marks = off[counters];
   Shared ctr, marks, ready;
   DevBuf doff;
-  Tab tab;
+  Tab<DevTab> tab;
   if (int e = ctr.create((size_t)counters * 4)) return e;
   if (int e = marks.create((size_t)n_marks * 4)) return e;
   if (int e = ready.create(128)) return e;
@@ -438,7 +337,7 @@ int run_ticket(const Ctx& c, uint32_t counters) {
           &c.out->host_ops_in_flight, &ms))
     return e;
   c.out->ms[1] += ms;
-  if (int e = tab.read()) return e;
+  if (int e = tab.read(c.st)) return e;
   const gm_hostsync_ticket_audit_t a = gm_hostsync_ticket_audit(
       (const uint32_t*)ctr.buf.p, n.data(), counters, (const uint32_t*)marks.buf.p, n_marks);
   c.out->tickets = c.ops();
@@ -499,7 +398,7 @@ int run_cas(const Ctx& c, uint32_t width, void* table_out) {
   gm_atomics_counts(c.total(), c.iters, width, count);
   Shared table, ready;
   DevBuf bounds;
-  Tab tab;
+  Tab<DevTab> tab;
   if (int e = table.create(bytes)) return e;
   if (int e = ready.create(128)) return e;
   GM_CHECK(bounds.alloc((size_t)width * 4));
@@ -522,7 +421,7 @@ int run_cas(const Ctx& c, uint32_t width, void* table_out) {
           &c.out->host_ops_in_flight, &ms))
     return e;
   c.out->ms[3] += ms;
-  if (int e = tab.read()) return e;
+  if (int e = tab.read(c.st)) return e;
   c.out->cas_giveups += tab.host.giveups;
   for (uint64_t v : gave) c.out->cas_giveups += v;
   c.out->cas_width = width;
@@ -540,27 +439,15 @@ int run_cas(const Ctx& c, uint32_t width, void* table_out) {
   return 0;
 }
 
-// wall_clock64() ticks in budget_us on the current device
-int budget_ticks_of(uint32_t budget_us, double* ticks_per_us, uint64_t* ticks) {
-  int dev = 0, khz = 0;
-  GM_CHECK(hipGetDevice(&dev));
-  GM_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-  if (khz <= 0) return (int)hipErrorInvalidDevice;
-  *ticks_per_us = khz / 1000.0;
-  *ticks = (uint64_t)(budget_us * *ticks_per_us + 0.5);
-  if (*ticks == 0) *ticks = 1;
-  return 0;
-}
-
 int run_handoff(const Ctx& c, uint32_t rounds, uint32_t lines, uint32_t budget_us,
                 uint32_t host_budget_us) {
-  const Inj inj = inj_for(c.inject, GM_HOSTSYNC_HANDOFF, 0);
+  const Inj inj = inj_for(c.inject, GM_HOSTSYNC_HANDOFF, 0, true);
   const size_t boxes = (size_t)c.blocks * rounds;
   double per_us = 0;
   uint64_t ticks = 0;
   if (int e = budget_ticks_of(budget_us, &per_us, &ticks)) return e;
   Shared pay_h, pay_d, flag_h, flag_d, ready;
-  Tab tab;
+  Tab<DevTab> tab;
   // failing data in every mailbox and no flag raised before the launch
   if (int e = pay_h.create(boxes * lines * 4096, 0xA5)) return e;
   if (int e = pay_d.create(boxes * lines * 4096, 0xA5)) return e;
@@ -607,7 +494,7 @@ int run_handoff(const Ctx& c, uint32_t rounds, uint32_t lines, uint32_t budget_u
           &unused, &ms))
     return e;
   c.out->ms[4] += ms;
-  if (int e = tab.read()) return e;
+  if (int e = tab.read(c.st)) return e;
   gm_hostsync_dir_t* h2d = &c.out->dir[0];
   gm_hostsync_dir_t* d2h = &c.out->dir[1];
   h2d->handoffs = tab.host.handoffs;

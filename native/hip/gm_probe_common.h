@@ -1,5 +1,6 @@
-// gm_probe_common.h — shared by the gfx950 probe translation units (gm_probe.hip, gm_gemm.hip,
-// gm_memtest.hip, gm_cuscan.hip, gm_hostlink.hip, gm_atomics.hip, gm_mfmascan.hip) and the
+// gm_probe_common.h — shared by every gfx950 probe translation unit (PROBE_SRC in native/Makefile:
+// gm_probe.hip includes it itself, the others through gm_pattern_stream.h, gm_gemm_shared.h,
+// gm_cuscan_frame.h or gm_atomics_dev.h) and the
 // block-scaled MFMA experiment: vector types, device selection guard, error macro, owning device /
 // pinned buffer, stream and events, and the two clocks (event pair, host monotonic).
 // Everything is in an anonymous namespace: each translation unit gets its own copy.

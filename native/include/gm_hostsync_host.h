@@ -1,6 +1,7 @@
 // gm_hostsync_host.h — the host threads' side of the host-sync test, in plain C++ with no HIP:
-// the operations a thread makes as a host-played block of the atomic tests, with the __atomic_*
-// builtins on the words the kernel works on at system scope, and the host half of the hand-off
+// the operations a thread makes as a host-played block of the atomic tests (the steps of
+// gm_atomics_steps.h with its __atomic_* policy, on the words the kernel works on at system
+// scope), and the host half of the hand-off
 // (produce, release the flag, acquire the reply's flag, compare). gm_hostsync.hip runs these in
 // std::threads against the kernel; native/tests/test_hostsync_host.cpp runs them against a CPU
 // stand-in for the kernel. Every wait here is bounded: the start by GM_HOSTSYNC_START_BOUND_US,
@@ -12,11 +13,7 @@
 #include <chrono>
 #include <vector>
 
-#include "gm_hostsync_ref.h"
-
-struct gm_hostsync_inj_t {
-  uint32_t a = 0, b = 0, word = 0, mask = 0, dir = 0, on = 0;  // on 0: none
-};
+#include "gm_atomics_steps.h"
 
 // What the launching thread and the host threads share besides the test's words. `ready` lies in
 // the memory the kernel writes; `done` and `abort` are the launching thread's.
@@ -45,28 +42,30 @@ inline bool gm_hostsync_in_flight(const gm_hostsync_gate_t* gate) {
   return __atomic_load_n(&gate->done, __ATOMIC_RELAXED) == 0;
 }
 
-// ---- the atomic tests: the thread plays block `vblock`, g = 256 vblock + t. Each returns the
-// operations it made while the kernel was still running.
+// ---- the atomic tests: the thread plays block `vblock`, g = 256 vblock + t, step by step with
+// the steps of gm_atomics_steps.h over gm_atomics_host_ops. Each returns the operations it made
+// while the kernel was still running.
+
+// step(g, s) for every thread t of the block, steps outermost as on the GPU
+template <class Step>
+inline uint64_t gm_hostsync_host_block(uint32_t vblock, uint32_t iters,
+                                       const gm_hostsync_gate_t* gate, Step step) {
+  uint64_t flying = 0;
+  for (uint32_t s = 0; s < iters; ++s)
+    for (uint32_t t = 0; t < GM_HOSTSYNC_THREADS; ++t) {
+      step(vblock * GM_HOSTSYNC_THREADS + t, s);
+      flying += gm_hostsync_in_flight(gate);
+    }
+  return flying;
+}
 
 // kind GM_ATOMICS_K_ADD_U32 or GM_ATOMICS_K_ADD_U64
 inline uint64_t gm_hostsync_host_add(uint32_t kind, void* table, uint32_t width, uint32_t vblock,
                                      uint32_t iters, uint64_t seed, const gm_hostsync_inj_t& inj,
                                      const gm_hostsync_gate_t* gate) {
-  uint64_t flying = 0;
-  for (uint32_t s = 0; s < iters; ++s)
-    for (uint32_t t = 0; t < GM_HOSTSYNC_THREADS; ++t) {
-      const uint32_t g = vblock * GM_HOSTSYNC_THREADS + t;
-      uint32_t h = gm_atomics_hash(seed, kind, 0, g, s);
-      if (inj.on && g == inj.a && s == inj.b) h ^= inj.mask;
-      const uint32_t w = gm_atomics_addr(g, s, width);
-      if (kind == GM_ATOMICS_K_ADD_U64)
-        (void)__atomic_fetch_add(&((uint64_t*)table)[w], gm_atomics_op64(seed, kind, h, g, s),
-                                 __ATOMIC_RELAXED);
-      else
-        (void)__atomic_fetch_add(&((uint32_t*)table)[w], h, __ATOMIC_RELAXED);
-      flying += gm_hostsync_in_flight(gate);
-    }
-  return flying;
+  return gm_hostsync_host_block(vblock, iters, gate, [&](uint32_t g, uint32_t s) {
+    gm_atomics_add_step<gm_atomics_host_ops>(kind, table, width, seed, inj, g, s);
+  });
 }
 
 // off[k] .. off[k + 1] are counter k's marks, n_marks in all
@@ -75,45 +74,21 @@ inline uint64_t gm_hostsync_host_ticket(uint32_t* ctr, const uint64_t* off, uint
                                         uint32_t iters, uint64_t seed,
                                         const gm_hostsync_inj_t& inj,
                                         const gm_hostsync_gate_t* gate, uint64_t* out_of_range) {
-  uint64_t flying = 0;
-  for (uint32_t s = 0; s < iters; ++s)
-    for (uint32_t t = 0; t < GM_HOSTSYNC_THREADS; ++t) {
-      const uint32_t g = vblock * GM_HOSTSYNC_THREADS + t;
-      const uint32_t d = gm_atomics_draw(gm_atomics_hash(seed, GM_ATOMICS_K_TICKET, 0, g, s));
-      const uint32_t k = gm_atomics_addr(g, s, counters);
-      const uint64_t base = off[k];
-      const uint64_t room =
-          base < n_marks && off[k + 1] - base <= n_marks - base ? off[k + 1] - base : 0;
-      const uint32_t old = __atomic_fetch_add(&ctr[k], d, __ATOMIC_RELAXED);
-      for (uint32_t i = 0; i < d; ++i) {
-        const uint64_t ticket = (uint64_t)old + i;
-        if (ticket < room)
-          (void)__atomic_fetch_add(&marks[base + ticket], 1u, __ATOMIC_RELAXED);
-        else
-          ++*out_of_range;
-      }
-      if (inj.on && g == inj.a && s == inj.b && old < room)
-        (void)__atomic_fetch_add(&marks[base + old], 1u, __ATOMIC_RELAXED);
-      flying += gm_hostsync_in_flight(gate);
-    }
-  return flying;
+  return gm_hostsync_host_block(vblock, iters, gate, [&](uint32_t g, uint32_t s) {
+    uint32_t old, d;
+    *out_of_range += gm_atomics_ticket_step<gm_atomics_host_ops>(ctr, off, marks, n_marks,
+                                                                 counters, seed, inj, g, s, old, d);
+  });
 }
 
 // returned: this thread's 256 * iters values, at t * iters + s
 inline uint64_t gm_hostsync_host_swap(uint32_t* words, uint32_t width, uint32_t vblock,
                                       uint32_t iters, const gm_hostsync_inj_t& inj,
                                       const gm_hostsync_gate_t* gate, uint32_t* returned) {
-  uint64_t flying = 0;
-  for (uint32_t s = 0; s < iters; ++s)
-    for (uint32_t t = 0; t < GM_HOSTSYNC_THREADS; ++t) {
-      const uint32_t g = vblock * GM_HOSTSYNC_THREADS + t;
-      uint32_t token = gm_hostsync_token(g, s);
-      if (inj.on && g == inj.a && s == inj.b) token ^= inj.mask;
-      returned[(size_t)t * iters + s] =
-          __atomic_exchange_n(&words[gm_atomics_addr(g, s, width)], token, __ATOMIC_RELAXED);
-      flying += gm_hostsync_in_flight(gate);
-    }
-  return flying;
+  return gm_hostsync_host_block(vblock, iters, gate, [&](uint32_t g, uint32_t s) {
+    returned[(size_t)(g - vblock * GM_HOSTSYNC_THREADS) * iters + s] =
+        gm_hostsync_swap_step<gm_atomics_host_ops>(words, width, inj, g, s);
+  });
 }
 
 // bound[w]: the operations into word w; a thread gives an operation up after that many failures
@@ -121,25 +96,9 @@ inline uint64_t gm_hostsync_host_cas(uint64_t* table, const uint32_t* bound, uin
                                      uint32_t vblock, uint32_t iters, uint64_t seed,
                                      const gm_hostsync_inj_t& inj, const gm_hostsync_gate_t* gate,
                                      uint64_t* giveups) {
-  uint64_t flying = 0;
-  for (uint32_t s = 0; s < iters; ++s)
-    for (uint32_t t = 0; t < GM_HOSTSYNC_THREADS; ++t) {
-      const uint32_t g = vblock * GM_HOSTSYNC_THREADS + t;
-      uint32_t h = gm_atomics_hash(seed, GM_ATOMICS_K_CAS, 0, g, s);
-      if (inj.on && g == inj.a && s == inj.b) h ^= inj.mask;
-      const uint64_t op = gm_atomics_op64(seed, GM_ATOMICS_K_CAS, h, g, s);
-      const uint32_t w = gm_atomics_addr(g, s, width);
-      uint64_t old = __atomic_load_n(&table[w], __ATOMIC_RELAXED);
-      uint32_t fails = 0;
-      while (!__atomic_compare_exchange_n(&table[w], &old, old + op, false, __ATOMIC_RELAXED,
-                                          __ATOMIC_RELAXED))
-        if (++fails >= bound[w]) {
-          ++*giveups;
-          break;
-        }
-      flying += gm_hostsync_in_flight(gate);
-    }
-  return flying;
+  return gm_hostsync_host_block(vblock, iters, gate, [&](uint32_t g, uint32_t s) {
+    *giveups += !gm_atomics_cas_step<gm_atomics_host_ops>(table, bound, width, seed, inj, g, s);
+  });
 }
 
 // ---- the hand-off. Mailbox m = b * rounds + r of either direction lies at word

@@ -1,12 +1,15 @@
 // The atomics test's host reference (include/gm_atomics_ref.h) on its own, under ASan/UBSan:
 // the folds against a second, differently ordered fold, the per-word counts against brute force,
-// the width rule and the caps, and what the reference refuses. No GPU, nothing else linked.
+// the width rule and the caps, and what the reference refuses; and the steps the kernels and the
+// host threads run (include/gm_atomics_steps.h) over a serial policy against that reference and
+// the host audits. No GPU, nothing else linked.
 #include <stdio.h>
 #include <string.h>
 
 #include <vector>
 
 #include "gm_atomics_ref.h"
+#include "gm_atomics_steps.h"
 
 static int failures = 0;
 #define CHECK(c)                                                  \
@@ -77,7 +80,152 @@ static void check_folds(uint32_t blocks, uint32_t iters, uint32_t spread) {
   }
 }
 
+// ---- the family's steps (include/gm_atomics_steps.h), which the kernels and the host threads
+// run, over a serial policy: plain reads and writes on one thread, every kind
+struct SerialOps {
+  static constexpr uint32_t kKinds = GM_ATOMICS_ADD_KINDS;
+  template <class T, class F>
+  static T apply(T* p, F f) {
+    const T old = *p;
+    *p = f(old);
+    return old;
+  }
+  template <class T>
+  static T fetch_add(T* p, T v) { return apply(p, [v](T o) { return (T)(o + v); }); }
+  static uint64_t fetch_xor(uint64_t* p, uint64_t v) {
+    return apply(p, [v](uint64_t o) { return o ^ v; });
+  }
+  static uint32_t fetch_max(uint32_t* p, uint32_t v) {
+    return apply(p, [v](uint32_t o) { return o > v ? o : v; });
+  }
+  static uint32_t fetch_min(uint32_t* p, uint32_t v) {
+    return apply(p, [v](uint32_t o) { return o < v ? o : v; });
+  }
+  static uint32_t fetch_and(uint32_t* p, uint32_t v) {
+    return apply(p, [v](uint32_t o) { return o & v; });
+  }
+  static uint32_t fetch_or(uint32_t* p, uint32_t v) {
+    return apply(p, [v](uint32_t o) { return o | v; });
+  }
+  // a bf16 is the upper half of an f32; the halves' sums stay within GM_ATOMICS_BF16_CAP = 128,
+  // integers of at most 8 significant bits, so adding in float and cutting is exact
+  static void pk_add_bf16(uint32_t* p, uint32_t lo, uint32_t hi) {
+    auto f32 = [](uint32_t bits) {
+      float f;
+      memcpy(&f, &bits, 4);
+      return f;
+    };
+    const float a = f32(*p << 16) + (float)lo, b = f32(*p & 0xFFFF0000u) + (float)hi;
+    *p = (gm_atomics_f32_bits(a) >> 16) | (gm_atomics_f32_bits(b) & 0xFFFF0000u);
+  }
+  static uint32_t exchange(uint32_t* p, uint32_t v) {
+    return apply(p, [v](uint32_t) { return v; });
+  }
+  static uint64_t load(const uint64_t* p) { return *p; }
+  static bool cas(uint64_t* p, uint64_t* old, uint64_t want) {
+    if (*p != *old) return *old = *p, false;
+    return *p = want, true;
+  }
+};
+
+// every (g, s) of the geometry through step(g, s)
+template <class Step>
+static void every_step(uint32_t blocks, uint32_t iters, Step step) {
+  for (uint32_t s = 0; s < iters; ++s)
+    for (uint32_t g = 0; g < blocks * GM_ATOMICS_THREADS; ++g) step(g, s);
+}
+
+// words of `kind`'s table after the steps that differ from the reference's clean table
+static uint32_t table_diff(uint32_t kind, uint32_t blocks, uint32_t iters, uint32_t width,
+                           const gm_atomics_inj_t& inj) {
+  const uint32_t wb = gm_atomics_is64(kind) ? 8 : 4;
+  // exactly the bytes a kernel's table has: ASan sees a step one word too far
+  std::vector<unsigned char> got((size_t)width * wb, (unsigned char)gm_atomics_init_byte(kind)),
+      want((size_t)width * wb);
+  gm_atomics_expected_host(kind, blocks, iters, width, kSeed, 0, 0, 0, want.data());
+  uint64_t giveups = 0;
+  if (kind == GM_ATOMICS_K_CAS) {
+    std::vector<uint32_t> bound;
+    gm_atomics_counts(blocks, iters, width, bound);
+    every_step(blocks, iters, [&](uint32_t g, uint32_t s) {
+      giveups += !gm_atomics_cas_step<SerialOps>((uint64_t*)got.data(), bound.data(), width, kSeed,
+                                                 inj, g, s);
+    });
+  } else {
+    every_step(blocks, iters, [&](uint32_t g, uint32_t s) {
+      gm_atomics_add_step<SerialOps>(kind, got.data(), width, kSeed, inj, g, s);
+    });
+  }
+  CHECK(giveups == 0);
+  uint32_t differ = 0;
+  for (uint32_t w = 0; w < width; ++w)
+    differ += memcmp(&got[(size_t)w * wb], &want[(size_t)w * wb], wb) != 0;
+  return differ;
+}
+
+// the ticket step over every (g, s): the host audit of its counters and marks
+static gm_hostsync_ticket_audit_t ticket_run(uint32_t blocks, uint32_t iters, uint32_t counters,
+                                             const gm_atomics_inj_t& inj) {
+  std::vector<uint32_t> n(counters);
+  gm_atomics_expected_host(GM_ATOMICS_K_TICKET, blocks, iters, counters, kSeed, 0, 0, 0, n.data());
+  std::vector<uint64_t> off((size_t)counters + 1, 0);
+  for (uint32_t k = 0; k < counters; ++k) off[k + 1] = off[k] + n[k];
+  std::vector<uint32_t> ctr(counters, 0), marks(off[counters], 0);
+  uint64_t out_of_range = 0, drawn = 0;
+  every_step(blocks, iters, [&](uint32_t g, uint32_t s) {
+    uint32_t old = ~0u, d = 0;
+    out_of_range += gm_atomics_ticket_step<SerialOps>(ctr.data(), off.data(), marks.data(),
+                                                      off[counters], counters, kSeed, inj, g, s,
+                                                      old, d);
+    CHECK(d >= 1 && d <= 4 && (uint64_t)old + d <= n[gm_atomics_addr(g, s, counters)]);
+    drawn += d;
+  });
+  CHECK(out_of_range == 0 && drawn == off[counters]);
+  return gm_hostsync_ticket_audit(ctr.data(), n.data(), counters, marks.data(), off[counters]);
+}
+
+static gm_hostsync_swap_audit_t swap_run(uint32_t blocks, uint32_t iters, uint32_t width,
+                                         const gm_atomics_inj_t& inj) {
+  std::vector<uint32_t> words(width, 0), ret((size_t)blocks * GM_ATOMICS_THREADS * iters);
+  every_step(blocks, iters, [&](uint32_t g, uint32_t s) {
+    ret[(size_t)g * iters + s] = gm_hostsync_swap_step<SerialOps>(words.data(), width, inj, g, s);
+  });
+  return gm_hostsync_swap_audit(blocks, iters, width, ret.data(), words.data());
+}
+
+static void check_steps(uint32_t blocks, uint32_t iters, uint32_t spread) {
+  const gm_atomics_inj_t none;
+  for (uint32_t kind = 0; kind <= GM_ATOMICS_K_CAS; ++kind) {
+    if (kind == GM_ATOMICS_K_TICKET) continue;
+    const uint32_t width = gm_atomics_width(kind, blocks, iters, spread);
+    CHECK(table_diff(kind, blocks, iters, width, none) == 0);
+  }
+  const gm_hostsync_ticket_audit_t t = ticket_run(blocks, iters, spread, none);
+  CHECK(t.holes == 0 && t.duplicates == 0 && t.counter_errors == 0 && t.first_index == ~0ull);
+  const gm_hostsync_swap_audit_t w = swap_run(blocks, iters, spread, none);
+  CHECK(w.missing == 0 && w.duplicates == 0 && w.foreign == 0);
+}
+
 int main() {
+  // the steps at the same shapes, and with a negative control at g = 300, s = 2: one word of
+  // add and CAS (the kinds where every mask changes the word), one duplicate ticket, one token
+  check_steps(1, 1, 1);
+  check_steps(2, 3, 64);
+  check_steps(9, 3, 1);
+  check_steps(9, 2, 4096);
+  {
+    gm_atomics_inj_t inj;
+    inj.a = 300, inj.b = 2, inj.mask = 0x10000u, inj.on = 1;
+    for (uint32_t kind : {(uint32_t)GM_ATOMICS_K_ADD_U32, (uint32_t)GM_ATOMICS_K_ADD_U64,
+                          (uint32_t)GM_ATOMICS_K_XOR_U64, (uint32_t)GM_ATOMICS_K_CAS})
+      CHECK(table_diff(kind, 2, 3, gm_atomics_width(kind, 2, 3, 64), inj) == 1);
+    const gm_hostsync_ticket_audit_t t = ticket_run(2, 3, 64, inj);
+    CHECK(t.duplicates == 1 && t.holes == 0 && t.counter_errors == 0);
+    inj.mask = 0x40000000u;  // no token of any thread of the run
+    const gm_hostsync_swap_audit_t w = swap_run(2, 3, 64, inj);
+    CHECK(w.missing == 1 && w.foreign == 1 && w.duplicates == 0);
+  }
+
   // geometry
   CHECK(gm_atomics_geometry_ok(1, 1) && gm_atomics_geometry_ok(4096, 64));
   CHECK(!gm_atomics_geometry_ok(0, 1) && !gm_atomics_geometry_ok(4097, 1));
