@@ -576,6 +576,13 @@ def probe() -> C.CDLL:
                                          C.POINTER(C.c_int)]
         lib.gm_probe_ldsscan_kernel_info.argtypes = [C.POINTER(C.c_int)] * 2
         lib.gm_probe_ldsscan_geometry.argtypes = [C.POINTER(C.c_uint32)] * 4
+        lib.gm_probe_sparsescan_expected.argtypes = lib.gm_probe_cuscan_expected.argtypes
+        lib.gm_probe_sparsescan_signature.argtypes = lib.gm_probe_cuscan_signature.argtypes
+        lib.gm_probe_sparsescan.argtypes = lib.gm_probe_cuscan.argtypes
+        lib.gm_probe_sparsescan_images.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32] + \
+            [C.POINTER(C.c_uint32)] * 4
+        lib.gm_probe_sparsescan_apply.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gm_probe_hostlink_geometry.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.gm_probe_hostlink_unroll.argtypes = [C.c_int]
         lib.gm_probe_hostlink_kwrite.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,

@@ -264,6 +264,12 @@ def _scans():
     return cuframe.scans()
 
 
+def _all_scans():
+    from gpumounter_amd.ops import cuframe
+
+    return cuframe.all_scans()
+
+
 def _scan_arg(scan, kind):
     """argparse type for a per-CU scan's options: the parser in the scan's module, its refusal a
     usage error."""
@@ -389,7 +395,7 @@ def cmd_probe(args) -> int:
 
     if _burn_in_usage(args, "probe"):
         return 2
-    cu, *later = _scans()             # the CU scan: before the host-link and atomics tests
+    cu, *later = _all_scans()         # the CU scan: before the host-link and atomics tests
     error = _scan_usage(cu, args, "probe")
     if error:
         print(error, file=sys.stderr)
@@ -718,7 +724,7 @@ def cmd_doctor(args) -> int:
         extra["host_sync"] = True
         if args.host_sync_inject:
             extra["host_sync_inject"] = args.host_sync_inject
-    scans = _scans()
+    scans = _all_scans()
     for scan in scans:
         error = _scan_usage(scan, args, "doctor")
         if error:
@@ -778,7 +784,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--memtest-flip", type=_memtest_arg("parse_flip"), default=None,
                    metavar="OFFSET:MASK",
                    help="negative control: corrupt that word after every fill; the test must fail")
-    cu, *later = _scans()
+    cu, *later = _all_scans()
     _add_probe_scan(p, cu)
     _add_hostlink_size(p, "host link (PCIe) test of every probed GPU over SIZE bytes of pinned "
                           "host memory per buffer (default 256M): checked transfers in both "

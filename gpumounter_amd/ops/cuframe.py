@@ -4,12 +4,12 @@ registers, 4 signature words per thread and test compared bit for bit with a tab
 host, and one result shape.
 
 A scan is a :class:`Scan` descriptor in its own module (``SCAN`` in :mod:`.cuscan`,
-:mod:`.mfmascan`, :mod:`.lanescan`, :mod:`.cachescan`, :mod:`.ldsscan`), next to its tables and the functions only
-it has. The descriptor's methods are everything the scans do alike: the name and bit lookups, the
+:mod:`.mfmascan`, :mod:`.lanescan`, :mod:`.cachescan`, :mod:`.ldsscan`, :mod:`.sparsescan`), next to its
+tables and the functions only it has. The descriptor's methods are everything the scans do alike: the name and bit lookups, the
 parsers, the argument checks, ``expected``, ``signature`` and ``scan``. The command line, ``doctor``
-and ``validate`` walk :func:`scans` and know no scan by name. Adding a scan: its kernel and
+and ``validate`` walk :func:`all_scans` and know no scan by name. Adding a scan: its kernel and
 host reference, a module with a ``SCAN`` and the public functions, its name in
-:data:`MORE_MODULES`, the three entry points in ``_native.py`` and its keyword parameters in ``doctor``.
+:data:`LATER_MODULES` (:data:`MODULES` and :data:`MORE_MODULES` are closed), the three entry points in ``_native.py`` and its keyword parameters in ``doctor``.
 
 Every refusal is made here, in Python, before the native library is reached.
 """
@@ -29,6 +29,7 @@ DEFAULT_SEED = 0x243F6A8885A308D3
 ANY = "any"
 MODULES = ("cuscan", "mfmascan", "lanescan", "cachescan")    # the order of every report
 MORE_MODULES = ("ldsscan",)     # the scans added since: they run and report after MODULES'
+LATER_MODULES = ("sparsescan",)     # and those added after that tier was pinned: after MORE_MODULES'
 
 
 def registry() -> Tuple["Scan", ...]:
@@ -38,10 +39,16 @@ def registry() -> Tuple["Scan", ...]:
 
 
 def scans() -> Tuple["Scan", ...]:
-    """Every scan's descriptor: :func:`registry`'s four, then those of :data:`MORE_MODULES`. This
-    is what the command line, ``doctor`` and ``validate`` walk."""
+    """:func:`registry`'s four descriptors, then those of :data:`MORE_MODULES`."""
     return registry() + tuple(importlib.import_module(f"{__package__}.{m}").SCAN
                               for m in MORE_MODULES)
+
+
+def all_scans() -> Tuple["Scan", ...]:
+    """Every scan's descriptor: those of :func:`scans`, then those of :data:`LATER_MODULES`. This
+    is what the command line, ``doctor`` and ``validate`` walk."""
+    return scans() + tuple(importlib.import_module(f"{__package__}.{m}").SCAN
+                           for m in LATER_MODULES)
 
 
 def decode_id(cu_id: int) -> Dict[str, int]:

@@ -42,7 +42,11 @@ starting a job on them — the reference offers nothing here:
 13. optionally (``--lds-scan``) the per-CU LDS scan on all GPUs at once
    (:func:`gpumounter_amd.ops.ldsscan.scan`): sub-dword, wide and paired LDS accesses, the LDS
    atomics, the bank crossbar at every conflict degree, the transposing read and direct
-   global-to-LDS loads on every compute unit.
+   global-to-LDS loads on every compute unit;
+14. optionally (``--sparse-scan``) the per-CU sparse and 32x32 matrix-core scan on all GPUs at once
+   (:func:`gpumounter_amd.ops.sparsescan.scan`): bit-exact 2:4 sparse SMFMACs in f16, bf16, i8,
+   fp8, bf8 and mixed fp8/bf8 at 16x16 and in f16, bf16, i8 and fp8 at 32x32 on every compute
+   unit.
 
 Prints one JSON document; exit code 0 only if every check passed. ``--cpu-ranks N`` runs step 3
 with N gloo ranks on the CPU (hermetic tests).
@@ -124,7 +128,7 @@ def main(argv=None) -> int:
     ap.add_argument("--memtest", nargs="?", const="auto", default=None, metavar="SIZE",
                     help="then the HBM pattern test on every GPU at once over SIZE bytes each "
                          "(64M, 8G; default: 90 %% of the free memory)")
-    cu, *later = cuframe.scans()      # the CU scan: before the host-link and atomics tests
+    cu, *later = cuframe.all_scans()  # the CU scan: before the host-link and atomics tests
     ap.add_argument("--cu-scan", action="store_true",
                     help=f"then the {cu.title} on every GPU at once")
     ap.add_argument("--host-link", nargs="?", const="auto", default=None, metavar="SIZE",

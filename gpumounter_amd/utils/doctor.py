@@ -306,7 +306,8 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
                cache_scan_inject=None, cache_scan_poke=None,
                burn_in_formats=("bf16",), lds_scan: bool = False,
                lds_scan_inject=None, lds_scan_poke=None, burn_in_attribute: bool = False,
-               burn_in_inject=None, host_sync: bool = False,
+               burn_in_inject=None, sparse_scan: bool = False,
+               sparse_scan_inject=None, host_sync: bool = False,
                host_sync_inject=None) -> List[Check]:
     """Run the gfx950 probe kernels on every GPU of the node (``doctor --gpu``): each amdsmi GPU
     must be visible to HIP and pass the wave64 liveness kernel. With ``burn_in_s`` also a
@@ -341,7 +342,10 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     ``cache_scan_inject`` and ``cache_scan_poke`` are its negative controls. With ``lds_scan``
     also the per-CU LDS scan (:func:`gpumounter_amd.ops.ldsscan.scan`: access widths, LDS atomics,
     bank crossbar, transposing read, global-to-LDS loads), failed, named and stated in the same
-    way; ``lds_scan_inject`` and ``lds_scan_poke`` are its negative controls. With ``host_sync``
+    way; ``lds_scan_inject`` and ``lds_scan_poke`` are its negative controls. With ``sparse_scan``
+    also the per-CU sparse and 32x32 matrix-core scan (:func:`gpumounter_amd.ops.sparsescan.scan`:
+    the 2:4 ``v_smfmac_*`` forms), after the LDS scan, failed, named with the format and stated in
+    the same way; ``sparse_scan_inject`` is its negative control. With ``host_sync``
     also the host-GPU atomics and hand-off test (:func:`gpumounter_amd.ops.hostsync.run`), after
     the atomics test: a wrong table word, a lost or doubled ticket, a missing, doubled or foreign
     swap value, a given-up CAS or a stale or lost hand-off word fails the check and names the
@@ -353,7 +357,7 @@ def check_gpus(cfg, burn_in_s: float = 0.0, *, memtest_bytes: int = 0,
     from gpumounter_amd.hw.inventory import Inventory
     from gpumounter_amd.ops import cuframe, mxgemm, probe
 
-    cu, *later = cuframe.scans()      # the CU scan: before the host-link and atomics tests
+    cu, *later = cuframe.all_scans()  # the CU scan: before the host-link and atomics tests
     try:
         n = probe.device_count()
     except Exception as e:  # noqa: BLE001 - no HIP runtime / driver
@@ -479,7 +483,8 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
         lane_scan_inject=None, cache_scan: bool = False, cache_scan_inject=None,
         cache_scan_poke=None, burn_in_formats=None, burn_in_flip=None,
         lds_scan: bool = False, lds_scan_inject=None, lds_scan_poke=None,
-        burn_in_attribute: bool = False, burn_in_inject=None, host_sync: bool = False,
+        burn_in_attribute: bool = False, burn_in_inject=None, sparse_scan: bool = False,
+        sparse_scan_inject=None, host_sync: bool = False,
         host_sync_inject=None) -> List[Check]:
     given = dict(locals())            # the scans' switches and controls, by parameter name
     from gpumounter_amd.ops import cuframe
@@ -506,7 +511,7 @@ def run(cfg, skip_cluster: bool = False, gpu: bool = False,
             extra["host_sync"] = True
             if host_sync_inject is not None:
                 extra["host_sync_inject"] = host_sync_inject
-        for scan in cuframe.scans():
+        for scan in cuframe.all_scans():
             if given[scan.stem]:
                 extra[scan.stem] = True
                 for name in scan.controls:     # the CU scan's are not among the parameters
